@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- compress MB/s of the MI355X NLZM path on the enwik9 configuration.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch-chunks B]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch-chunks B] [--dump-outputs DIR] [--full]
 
 Workload (BASELINE.json configs[3], the configuration the metric is quoted on): the WHOLE 1,000,000,000-byte
 stream at -window:28, synthetic stand-in for enwik9 (nlzm_amd/corpus.syn_text; the real file is used when
@@ -10,17 +10,27 @@ so a *step* is a fixed slice of it: 1/25 of its persistent launches (41 launches
 chunk = 122,368 input bytes = one frame, NLZM.cpp:1724), each launch = pre-pass kernels, the persistent
 match-find/parse/emit kernel, rANS-coding of the launch's frames and their gather into the output stream.
 `--steps 20 --warmup 5` (what the driver runs) therefore covers the stream from its first byte to its last: the
-warm-up steps are the first 200 MB, the timed steps the other 800 MB, and when the last step has run the stream is
-finished, hashed and compared with the REFERENCE's own stream for this input (tests/golden/full.json, made by
-oracle/make_golden_full.py from the compiled reference): `config.bit_exact`.  Fewer steps time a prefix of the same
-stream and say so (`bit_exact` null: there is nothing to compare a prefix with).  The input is resident in HBM
-before the timed region starts.
+warm-up steps are the first 200 MB, the timed steps the other 800 MB.  Fewer steps time a prefix of the same
+stream and say so.  When more steps are asked for than one stream holds, a step is cut to 1/(K + W) of the launches,
+so that exactly K steps are timed.  The input is resident in HBM before the timed region starts.
+
+A plain run does only what the headline needs: set up, warm up, time the K steps, print the JSON line (`metric`,
+`value`, `unit`, `higher_is_better`, `dtype`, `ms_per_step` = one timed step in milliseconds, `config`).
+--dump-outputs DIR then also writes what the last timed step gave its caller: DIR/last_step_stream.npy, the stream
+bytes that step appended (float32; above 12 Mi bytes a fixed sample of them, the positions drawn by
+numpy.random.default_rng(0).choice(len, 12 Mi, replace=False), sorted), and DIR/last_step_counts.npy, the
+(in_done, out_done, finished) the step returned (float64).  With N > 1 every rank writes its own, suffixed _rank<r>.
+
+--full adds everything else, none of it inside the timed region: when the last step has finished the stream it is
+hashed and compared with the REFERENCE's own stream for this input (tests/golden/full.json, made by
+oracle/make_golden_full.py from the compiled reference): `config.bit_exact` (null for a prefix: there is nothing to
+compare it with).
 
 With N > 1 (one process per GPU, torchrun) the input is N independent blocks of 1e9/N bytes, one stream per GPU
 (SURVEY.md 8e); there is no data-path collective, only the final gather of the streams over RCCL, which is inside
 the timed region.  value = input bytes all ranks consumed in the timed steps / max-rank time.
 
-The JSON line also carries:
+With --full the JSON line also carries:
   roofline      dominant kernel (pipeline2_kernel) against the HBM roof: algorithmic bytes per launch from
                 the device's own operation counters / the kernel's mean launch time measured
                 with HIP events on the library's stream; peak_measured = a device copy on this GPU; b_min = the bytes
@@ -69,6 +79,7 @@ CHUNK = 122_368
 STEPS_PER_STREAM = 25      # a step is 1/25 of the stream's launches: --steps 20 --warmup 5 is the whole stream
 HBM_PEAK_GBS = 8000.0      # MI355X_MICROARCH.md: 8 TB/s HBM3E
 BLOCKS_BATCH = 8           # block-mode leg: chunks of every block per shared persistent launch
+MAX_DUMP_BYTES = 48 << 20  # --dump-outputs: float32 stream bytes written at most (a step of 8-chunk launches gives ~8 MB of stream)
 
 
 def algorithmic_bytes(st: dict) -> int:
@@ -223,6 +234,91 @@ def copy_peak_gbs(torch, dev) -> float:
     return 5 * 2 * n / (e0.elapsed_time(e1) * 1e-3) / 1e9
 
 
+def stand_in(size: int, seed: int, workers: int) -> np.ndarray:
+    """corpus.syn_text(size, seed), the same bytes, with its text blocks -- nearly all of its time -- made by `workers` processes at
+    once (syn_text on one core takes 14 - 40 s for the 1e9-byte stand-in, depending on the host).  syn_text asks _text_block for
+    8 MiB blocks until the rest is shorter, and a block of that size always takes the same 2 * ntok doubles of the generator's
+    stream (rng.random(ntok) and rng.choice(4, ntok, p)): block i starts i * 2 * ntok draws after the vocabulary, wherever it lands
+    in the output.  The workers make those blocks; syn_text then runs as usual, its _text_block replaced by a lookup that hands
+    back the finished block and skips the same draws (any other request, such as the short last one, is made there and then),
+    and applies its overwrite events itself.  Forks: call it before the GPU is touched.  tests/test_bench_input.py holds it to
+    syn_text."""
+    import mmap
+
+    blk = 8 << 20                                   # syn_text's request size
+    ntok = int(blk / 6.5) + 64                      # corpus._text_block's token count for it
+    nblk = int(size / (1.2 * blk))                  # blocks of that size syn_text asks for (each gives ~1.29 x blk bytes); a short guess costs time only
+    if workers < 2 or nblk < 2:
+        return corpus.syn_text(size, seed)
+    rng = np.random.default_rng(seed)
+    vocab = corpus._vocab(rng)
+    p = 1.0 / np.arange(1, len(vocab[1]) + 1) ** 1.1
+    cdf = np.cumsum(p / p.sum())
+    state = rng.bit_generator.state                 # after the vocabulary: where the first block starts
+
+    def skip(bitgen, k):                            # advance() drops a buffered 32-bit half; the text draws never use it, later draws may
+        st = bitgen.state
+        bitgen.advance(k)
+        moved = bitgen.state
+        moved["has_uint32"], moved["uinteger"] = st["has_uint32"], st["uinteger"]
+        bitgen.state = moved
+
+    slot = 2 * blk
+    text = np.frombuffer(mmap.mmap(-1, nblk * slot), dtype=np.uint8)     # shared with the workers
+    lens = np.frombuffer(mmap.mmap(-1, nblk * 8), dtype=np.int64)
+    pids = []
+    for w in range(workers):
+        pid = os.fork()
+        if pid == 0:
+            code = 1
+            try:
+                for i in range(w, nblk, workers):
+                    g = np.random.PCG64()
+                    g.state = state
+                    skip(g, i * 2 * ntok)
+                    b = corpus._text_block(np.random.Generator(g), vocab, cdf, blk)
+                    text[i * slot:i * slot + len(b)] = b          # (raises past the slot)
+                    lens[i] = len(b)
+                code = 0
+            except BaseException:
+                import traceback
+                traceback.print_exc()
+            finally:
+                os._exit(code)
+        pids.append(pid)
+    failed = [pid for pid in pids if os.waitpid(pid, 0)[1] != 0]
+    if failed:
+        raise RuntimeError(f"stand_in: {len(failed)} of {workers} workers failed")
+
+    orig = corpus._text_block
+    made = iter(range(nblk))
+
+    def lookup(r, vocab_, cdf_, nbytes):
+        i = next(made, None) if nbytes == blk else None
+        if i is None:
+            return orig(r, vocab_, cdf_, nbytes)
+        skip(r.bit_generator, 2 * ntok)
+        return text[i * slot:i * slot + lens[i]]
+
+    corpus._text_block = lookup
+    try:
+        return corpus.syn_text(size, seed)
+    finally:
+        corpus._text_block = orig
+
+
+def dump_last_step(out_dir: str, produced, counts, suffix: str, max_bytes: int) -> None:
+    """--dump-outputs: the stream bytes the last timed step appended (a uint8 device tensor) as float32, a fixed seeded sample of
+    them when there are more than max_bytes / 4, and what the step returned (in_done, out_done, finished) as float64."""
+    os.makedirs(out_dir, exist_ok=True)
+    host = produced.cpu().numpy()
+    cap = max_bytes // 4
+    if host.size > cap:
+        host = host[np.sort(np.random.default_rng(0).choice(host.size, cap, replace=False))]
+    np.save(os.path.join(out_dir, f"last_step_stream{suffix}.npy"), host.astype(np.float32))
+    np.save(os.path.join(out_dir, f"last_step_counts{suffix}.npy"), np.array(counts, dtype=np.float64))
+
+
 def blocks_leg(lib, torch, dev, d_in, n: int, k: int, B: int, steps: int, warmup: int, check: bool) -> dict:
     """The path's shard axis inside ONE GPU: this rank's n input bytes split into k independent blocks,
     every block's NLZM stream in flight at once (three stage CUs + worker CUs each, shared persistent launches).  Steps
@@ -356,16 +452,19 @@ def main():
     ap.add_argument("--steps", type=int, default=3)
     ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--batch-chunks", type=int, default=8)
-    ap.add_argument("--cpu-sample-mb", type=float, default=25.0, help="size of the CPU leg's small sample (a prefix of the stream as a file of its own)")
-    ap.add_argument("--cpu-deep-mb", type=float, default=280.0, help="size of the CPU leg's sample at the headline's depth (> 2^28 bytes keeps -window:28)")
-    ap.add_argument("--no-cpu", action="store_true")
-    ap.add_argument("--no-workloads", action="store_true", help="skip the real-text and markup workloads that follow the headline (about 3 minutes)")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write what the last timed step returned as DIR/<name>.npy")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the checks and legs beside the headline: reference comparison, roofline, CPU baseline, block mode, workloads")
+    ap.add_argument("--cpu-sample-mb", type=float, default=25.0, help="(--full) size of the CPU leg's small sample (a prefix of the stream as a file of its own)")
+    ap.add_argument("--cpu-deep-mb", type=float, default=280.0, help="(--full) size of the CPU leg's sample at the headline's depth (> 2^28 bytes keeps -window:28)")
+    ap.add_argument("--no-cpu", action="store_true", help="(--full) skip the CPU baseline")
+    ap.add_argument("--no-workloads", action="store_true", help="(--full) skip the real-text and markup workloads that follow the headline (about 3 minutes)")
     ap.add_argument("--block-streams", type=int, default=32,
-                    help="also time the independent-block mode with this many streams in flight on each GPU (0: skip)")
+                    help="(--full) also time the independent-block mode with this many streams in flight on each GPU (0: skip)")
     args = ap.parse_args()
-
-    import torch
-    import torch.distributed as dist
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    full = args.full
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -373,15 +472,7 @@ def main():
     if world != args.gpus:
         if args.gpus != 1 or world != 1:
             raise SystemExit(f"--gpus {args.gpus} but WORLD_SIZE={world}: launch with torch.distributed.run --nproc-per-node {args.gpus}")
-    torch.cuda.set_device(local_rank)
-    dev = torch.device("cuda", local_rank)
-    if world > 1:
-        dist.init_process_group("nccl", rank=rank, world_size=world, device_id=dev)
-
-    nlzm_amd.init(local_rank)          # fails loudly without the HIP extension / a gfx950 device
-    lib = nlzm_amd.load_library()
     B = args.batch_chunks
-    nlzm_amd.set_option("batch_chunks", B)
 
     lo, hi = shard.block_range(STREAM_BYTES, world, rank)
     n = hi - lo
@@ -389,25 +480,42 @@ def main():
     nlaunch = -(-nchunks // B)
     per_step = -(-nlaunch // STEPS_PER_STREAM)           # launches per step
     steps_total = args.steps + args.warmup
-    whole = steps_total * per_step >= nlaunch
-    need = n if whole or args.block_streams > 0 else min(n, steps_total * per_step * B * CHUNK + (1 << 20))
+    if steps_total > -(-nlaunch // per_step):
+        # (more steps than one stream holds at that size: shorter steps, so that every one asked for runs)
+        per_step = nlaunch // steps_total
+        if per_step < 1:
+            raise SystemExit(f"--steps + --warmup = {steps_total}, but the stream has only {nlaunch} launches of {B} chunks")
 
-    # ---- synthetic input of the stream's shape, resident in HBM before timing -----------------------
+    # ---- synthetic input of the stream's shape, made before the GPU is touched (stand_in forks), resident in HBM before timing ----
+    # (all n bytes even when the steps read a prefix: syn_text's bytes depend on the size asked for, so a shorter call would
+    # not give the stream's first bytes)
     real = os.path.join(os.environ.get("NLZM_CORPUS_DIR", "/nonexistent"), "enwik9")
     if os.path.exists(real):
-        host = np.fromfile(real, dtype=np.uint8, count=need, offset=lo)
+        host = np.fromfile(real, dtype=np.uint8, count=n, offset=lo)
         data_kind = "file:enwik9"
     else:
         # N = 1: the 1e9-byte stand-in; N > 1: every block is its own seeded text of the same kind (blocks are
         # independent streams anyway, and this avoids generating up to 875 MB per rank to skip over)
-        host = corpus.syn_text(need, corpus.SEED + rank)
+        host = stand_in(n, corpus.SEED + rank, min(16, len(os.sched_getaffinity(0))) // world)
         data_kind = "synthetic"
+
+    import torch
+    import torch.distributed as dist
+
+    torch.cuda.set_device(local_rank)
+    dev = torch.device("cuda", local_rank)
+    if world > 1:
+        dist.init_process_group("nccl", rank=rank, world_size=world, device_id=dev)
+
+    nlzm_amd.init(local_rank)          # fails loudly without the HIP extension / a gfx950 device
+    lib = nlzm_amd.load_library()
+    nlzm_amd.set_option("batch_chunks", B)
+
     cpu_leg = None
-    if world == 1 and not args.no_cpu:
-        # (needs the bytes on the host: a run of a few steps generates a prefix only, and the CPU leg takes what there is)
+    if full and world == 1 and not args.no_cpu:
         cpu_leg = CpuBaseline(host, int(args.cpu_deep_mb * 1e6), int(args.cpu_sample_mb * 1e6))
-    d_in = torch.zeros(n + 4096, dtype=torch.uint8, device=dev)     # bytes past `need` are never read by the timed steps
-    d_in[:need].copy_(torch.from_numpy(host[:need]))
+    d_in = torch.zeros(n + 4096, dtype=torch.uint8, device=dev)
+    d_in[:n].copy_(torch.from_numpy(host))
     cap = int(lib.nlzm_hip_compress_bound(n))
     d_out = torch.empty(cap, dtype=torch.uint8, device=dev)
     torch.cuda.synchronize()
@@ -429,8 +537,9 @@ def main():
         if not fin.value:
             step()
     torch.cuda.synchronize()
-    st0, tm0 = nlzm_amd.stats(), nlzm_amd.timing()
-    sc0 = stage_counters()
+    if full:
+        st0, tm0 = nlzm_amd.stats(), nlzm_amd.timing()
+        sc0 = stage_counters()
     in0, out0 = in_done.value, out_done.value
 
     if world > 1:
@@ -438,9 +547,11 @@ def main():
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     done_steps = 0
+    last_out0 = out0
     for _ in range(args.steps):
         if fin.value:
             break
+        last_out0 = out_done.value
         step()
         done_steps += 1
     if world > 1:
@@ -451,12 +562,17 @@ def main():
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
 
-    st1, tm1 = nlzm_amd.stats(), nlzm_amd.timing()
-    sc1 = stage_counters()
+    if args.dump_outputs:
+        dump_last_step(args.dump_outputs, d_out[last_out0:out_done.value], (in_done.value, out_done.value, fin.value),
+                       "" if world == 1 else f"_rank{rank}", MAX_DUMP_BYTES // world)
+
+    if full:
+        st1, tm1 = nlzm_amd.stats(), nlzm_amd.timing()
+        sc1 = stage_counters()
 
     # ---- the stream is complete: the reference's bytes? ------------------------------------------------------------
     bit_exact, stream_len, stream_sha = None, None, None
-    if fin.value:
+    if full and fin.value:
         dst_len = C.c_uint64(0)
         if lib.nlzm_hip_stream_finish(C.byref(dst_len)):
             raise SystemExit(f"stream_finish failed: {lib.nlzm_hip_last_error().decode()}")
@@ -471,7 +587,7 @@ def main():
 
     # ---- block mode inside each GPU ----------------------------------------------------------------------------------
     blocks = None
-    if args.block_streams > 0:
+    if full and args.block_streams > 0:
         del d_out
         torch.cuda.empty_cache()
         blocks = blocks_leg(lib, torch, dev, d_in, n, args.block_streams, B, args.steps, args.warmup,
@@ -480,7 +596,7 @@ def main():
 
     # ---- the inputs the stand-in flatters the pipeline on: real text (source code) and wiki-shaped markup, whole streams ------------------------------
     workloads = None
-    if world == 1 and not args.no_workloads:
+    if full and world == 1 and not args.no_workloads:
         try:
             del d_out
         except NameError:
@@ -490,14 +606,6 @@ def main():
         workloads = workloads_leg(lib, torch, dev)
 
     if rank == 0:
-        d = {k: st1[k] - st0[k] for k in ("bt_calls", "bt_tests", "cmp_bytes", "ht_rows", "rk_probes", "rk_inserts",
-                                          "positions", "uncertain_positions")}
-        d["in_bytes_step"] = in_done.value - in0
-        d["out_bytes_step"] = out_done.value - out0
-        launches = max(1, tm1["match_parse_launches"] - tm0["match_parse_launches"])
-        k_ms = (tm1["match_parse_ms"] - tm0["match_parse_ms"]) / launches
-        b_alg = algorithmic_bytes(d) / launches
-        achieved = b_alg / (k_ms * 1e-3) / 1e9 if k_ms > 0 else 0.0
         first_b, last_b = in0, in_done.value
         res = {
             "metric": "compress MB/s", "value": round(total_in / 1e6 / tmax, 4), "unit": "MB/s", "n_gpus": world,
@@ -510,68 +618,80 @@ def main():
                                f"syn_text({n}, SEED + r) -- the same kind and amount of work as byte range r of the 1e9-byte stand-in, not those bytes; "
                                f"its reference stream is in tests/golden/gpus.json)" if world > 1 else "")
                             + f"; step = {per_step} launches of {B} chunks ({per_step * B * CHUNK} B) of the stream; timed: bytes "
-                              f"[{first_b}, {last_b}) of {n}" + (", i.e. to the end of the stream" if fin.value else " (a prefix: fewer than 25 steps were asked for)"),
+                              f"[{first_b}, {last_b}) of {n}" + (", i.e. to the end of the stream" if fin.value else " (a prefix: the steps asked for end before the stream does)"),
                 "window_bits": WINDOW, "batch_chunks": B, "launches_per_step": per_step, "bytes_timed": int(total_in),
-                "whole_stream": bool(fin.value), "bit_exact": bit_exact,
+                "whole_stream": bool(fin.value),
+            },
+        }
+        if full:
+            res["config"].update({
+                "bit_exact": bit_exact,
                 "ranks_checked": ranks_checked,
                 "bit_exact_against": (("tests/golden/full.json" if world == 1 else "tests/golden/gpus.json") + " (the reference's own stream for this input" + (", every rank's block)" if world > 1 else ")") if bit_exact is not None
-                                      else "nothing: " + ("a prefix has no reference stream; run --steps 20 --warmup 5" if not fin.value else "no reference stream for this input")),
+                                      else "nothing: " + ("a prefix has no reference stream; run --full --steps 20 --warmup 5" if not fin.value else "no reference stream for this input")),
                 "stream_bytes": stream_len, "stream_sha256": stream_sha,
-            },
-            "roofline": {"bound": "hbm", "kernel": "pipeline2_kernel", "achieved": round(achieved, 4), "peak": HBM_PEAK_GBS,
-                         "unit": "GB/s", "frac": round(achieved / HBM_PEAK_GBS, 8), "traffic": None,
-                         "peak_measured": round(copy_peak_gbs(torch, dev), 1),
-                         "algorithmic_bytes_per_launch": int(b_alg), "kernel_ms_per_launch": round(k_ms, 3),
-                         "launches_timed": int(launches),
-                         "b_min_bytes_per_launch": int((d["in_bytes_step"] + d["out_bytes_step"]) / launches),
-                         "algorithmic_bytes_per_input_byte": round(algorithmic_bytes(d) / max(1, d["in_bytes_step"]), 2),
-                         "algorithmic_bytes_line_granular": int(algorithmic_bytes_lines(d) / launches),
-                         "frac_line_granular": round(algorithmic_bytes_lines(d) / launches / (k_ms * 1e-3) / 1e9 / HBM_PEAK_GBS, 8) if k_ms > 0 else 0.0,
-                         "latency_bound": latency_bound(sc0, sc1),
-                         # (SURVEY 8d defines cmp_bytes as the iterations of the reference's compare loop, NLZM.cpp:863; the device counts the oracle's
-                         #  cmp_bytes_needed -- an explicit rep probe measured up to the 264 bytes that can matter, the reference compares up to 4,096 and then
-                         #  caps the length, :1605-1606.  The oracle counts both: 1,039,103,767 against 1,087,452,480 on the first 16 MB of this workload at
-                         #  -window:28, identical on markup; 2 x cmp_bytes is 28 % of the algorithmic bytes)
-                         "cmp_bytes_definition": {"counted": "oracle cmp_bytes_needed (rep probes up to 264 bytes)", "ratio_to_reference_loop_iterations": 0.9555,
-                                                  "measured_on": "corpus.syn_text(16e6) at -window:28, tests/oracle_py.compress(want_stats=True)"}},
-            "kernel_ms": {"prep": round(tm1["prep_ms"] - tm0["prep_ms"], 3),
-                          "match_parse": round(tm1["match_parse_ms"] - tm0["match_parse_ms"], 3),
-                          "rans_gather": round(tm1["rans_ms"] - tm0["rans_ms"], 3)},
-            "counters": d,
-        }
-        res["roofline"]["latency_bound"]["bt4"]["tests_per_call"] = round(d["bt_tests"] / max(1, d["bt_calls"]), 1)
-        if bit_exact is False:
-            errors.append("the stream differs from the reference's")
-        # HBM traffic of the same command, measured in separate rocprofv3 --pmc passes (tests/prof_run.sh) and
-        # committed under profiles/: bench.py itself cannot read PMC counters
-        try:
-            import glob
-            prof = sorted(glob.glob(os.path.join(ROOT, "profiles", "r*_pmc_summary.json")))[-1]
-            pj = json.load(open(prof))
-            if pj.get("kernel") == "pipeline2_kernel" and pj["bench_line_under_profiler"]["config"]["batch_chunks"] == B and world == 1:
-                if pj.get("csrc_sha16") != csrc_sha16():
-                    # (counters of other kernels than the ones timed here: not this run's traffic)
-                    res["roofline"]["traffic_source"] = os.path.relpath(prof, ROOT) + " refused: recorded for other kernel sources (csrc_sha16 differs)"
-                else:
-                    t = pj["traffic_bytes_per_launch"]
-                    res["roofline"]["traffic"] = int(t.get("total_calibrated", t["total_with_fetch_x2"]))
-                    res["roofline"]["traffic_source"] = os.path.relpath(prof, ROOT) + (" (FETCH_SIZE calibrated on random 8-byte reads)" if "total_calibrated" in t else " (FETCH_SIZE x 2)")
-        except Exception:
-            pass
-        res["cpu_baseline"] = cpu_leg.collect() if cpu_leg is not None else None
-        if blocks is not None:
-            res["blocks"] = blocks
-            if "error" in blocks:
-                errors.append("blocks: " + blocks["error"])
-        if workloads is not None:
-            res["workloads"] = workloads
-            for name, w in workloads.items():
-                if isinstance(w, dict) and (w.get("error") or w.get("bit_exact") is False):
-                    errors.append(f"workload {name}: " + (w.get("error") or "the stream differs from the reference's"))
-        try:
-            res["gpu_max_hw_queues_effective"] = nlzm_amd.counter("gpu_max_hw_queues_effective")     # (4: the HIP runtime had started before the variable was set -- block mode then runs ~30 % slower)
-        except nlzm_amd.NlzmError:
-            pass
+            })
+            d = {k: st1[k] - st0[k] for k in ("bt_calls", "bt_tests", "cmp_bytes", "ht_rows", "rk_probes", "rk_inserts",
+                                              "positions", "uncertain_positions")}
+            d["in_bytes_step"] = in_done.value - in0
+            d["out_bytes_step"] = out_done.value - out0
+            launches = max(1, tm1["match_parse_launches"] - tm0["match_parse_launches"])
+            k_ms = (tm1["match_parse_ms"] - tm0["match_parse_ms"]) / launches
+            b_alg = algorithmic_bytes(d) / launches
+            achieved = b_alg / (k_ms * 1e-3) / 1e9 if k_ms > 0 else 0.0
+            res["roofline"] = {"bound": "hbm", "kernel": "pipeline2_kernel", "achieved": round(achieved, 4), "peak": HBM_PEAK_GBS,
+                               "unit": "GB/s", "frac": round(achieved / HBM_PEAK_GBS, 8), "traffic": None,
+                               "peak_measured": round(copy_peak_gbs(torch, dev), 1),
+                               "algorithmic_bytes_per_launch": int(b_alg), "kernel_ms_per_launch": round(k_ms, 3),
+                               "launches_timed": int(launches),
+                               "b_min_bytes_per_launch": int((d["in_bytes_step"] + d["out_bytes_step"]) / launches),
+                               "algorithmic_bytes_per_input_byte": round(algorithmic_bytes(d) / max(1, d["in_bytes_step"]), 2),
+                               "algorithmic_bytes_line_granular": int(algorithmic_bytes_lines(d) / launches),
+                               "frac_line_granular": round(algorithmic_bytes_lines(d) / launches / (k_ms * 1e-3) / 1e9 / HBM_PEAK_GBS, 8) if k_ms > 0 else 0.0,
+                               "latency_bound": latency_bound(sc0, sc1),
+                               # (SURVEY 8d defines cmp_bytes as the iterations of the reference's compare loop, NLZM.cpp:863; the device counts the oracle's
+                               #  cmp_bytes_needed -- an explicit rep probe measured up to the 264 bytes that can matter, the reference compares up to 4,096 and then
+                               #  caps the length, :1605-1606.  The oracle counts both: 1,039,103,767 against 1,087,452,480 on the first 16 MB of this workload at
+                               #  -window:28, identical on markup; 2 x cmp_bytes is 28 % of the algorithmic bytes)
+                               "cmp_bytes_definition": {"counted": "oracle cmp_bytes_needed (rep probes up to 264 bytes)", "ratio_to_reference_loop_iterations": 0.9555,
+                                                        "measured_on": "corpus.syn_text(16e6) at -window:28, tests/oracle_py.compress(want_stats=True)"}}
+            res["kernel_ms"] = {"prep": round(tm1["prep_ms"] - tm0["prep_ms"], 3),
+                                "match_parse": round(tm1["match_parse_ms"] - tm0["match_parse_ms"], 3),
+                                "rans_gather": round(tm1["rans_ms"] - tm0["rans_ms"], 3)}
+            res["counters"] = d
+            res["roofline"]["latency_bound"]["bt4"]["tests_per_call"] = round(d["bt_tests"] / max(1, d["bt_calls"]), 1)
+            if bit_exact is False:
+                errors.append("the stream differs from the reference's")
+            # HBM traffic of the same command, measured in separate rocprofv3 --pmc passes (tests/prof_run.sh) and
+            # committed under profiles/: bench.py itself cannot read PMC counters
+            try:
+                import glob
+                prof = sorted(glob.glob(os.path.join(ROOT, "profiles", "r*_pmc_summary.json")))[-1]
+                pj = json.load(open(prof))
+                if pj.get("kernel") == "pipeline2_kernel" and pj["bench_line_under_profiler"]["config"]["batch_chunks"] == B and world == 1:
+                    if pj.get("csrc_sha16") != csrc_sha16():
+                        # (counters of other kernels than the ones timed here: not this run's traffic)
+                        res["roofline"]["traffic_source"] = os.path.relpath(prof, ROOT) + " refused: recorded for other kernel sources (csrc_sha16 differs)"
+                    else:
+                        t = pj["traffic_bytes_per_launch"]
+                        res["roofline"]["traffic"] = int(t.get("total_calibrated", t["total_with_fetch_x2"]))
+                        res["roofline"]["traffic_source"] = os.path.relpath(prof, ROOT) + (" (FETCH_SIZE calibrated on random 8-byte reads)" if "total_calibrated" in t else " (FETCH_SIZE x 2)")
+            except Exception:
+                pass
+            res["cpu_baseline"] = cpu_leg.collect() if cpu_leg is not None else None
+            if blocks is not None:
+                res["blocks"] = blocks
+                if "error" in blocks:
+                    errors.append("blocks: " + blocks["error"])
+            if workloads is not None:
+                res["workloads"] = workloads
+                for name, w in workloads.items():
+                    if isinstance(w, dict) and (w.get("error") or w.get("bit_exact") is False):
+                        errors.append(f"workload {name}: " + (w.get("error") or "the stream differs from the reference's"))
+            try:
+                res["gpu_max_hw_queues_effective"] = nlzm_amd.counter("gpu_max_hw_queues_effective")     # (4: the HIP runtime had started before the variable was set -- block mode then runs ~30 % slower)
+            except nlzm_amd.NlzmError:
+                pass
         if errors:
             res["error"] = "; ".join(errors)
         print(json.dumps(res))

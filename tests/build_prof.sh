@@ -4,8 +4,8 @@
 #  nlzm_amd/libnlzm_exp_prof.so -- and load it through NLZM_LIB; the profile build also counts what a hot bin's wave spends its steps on, by section)
 set -e
 cd "$(dirname "$0")/../nlzm_amd/csrc"
-mkdir -p /tmp/nlzm_prof_build
-/opt/rocm/bin/hipcc -DNLZM_PROFILE $EXTRA -O3 -std=c++17 -fPIC --offload-arch=gfx950 -Wno-unused-function -Wno-unused-variable -c -o /tmp/nlzm_prof_build/k.o nlzm_kernels.hip &
-/opt/rocm/bin/hipcc -DNLZM_PROFILE $EXTRA -O3 -std=c++17 -fPIC --offload-arch=gfx950 -Wno-unused-function -Wno-unused-variable -Wno-undefined-inline -x hip -c -o /tmp/nlzm_prof_build/h.o nlzm_hip.cpp &
+d=$(mktemp -d); trap 'rm -rf "$d"' EXIT
+/opt/rocm/bin/hipcc -DNLZM_PROFILE $EXTRA -O3 -std=c++17 -fPIC --offload-arch=gfx950 -Wno-unused-function -Wno-unused-variable -c -o $d/k.o nlzm_kernels.hip &
+/opt/rocm/bin/hipcc -DNLZM_PROFILE $EXTRA -O3 -std=c++17 -fPIC --offload-arch=gfx950 -Wno-unused-function -Wno-unused-variable -Wno-undefined-inline -x hip -c -o $d/h.o nlzm_hip.cpp &
 wait
-/opt/rocm/bin/hipcc -shared -fPIC --offload-arch=gfx950 -o ../libnlzm_hip_prof.so /tmp/nlzm_prof_build/k.o /tmp/nlzm_prof_build/h.o
+/opt/rocm/bin/hipcc -shared -fPIC --offload-arch=gfx950 -o ../libnlzm_hip_prof.so $d/k.o $d/h.o

@@ -3,7 +3,7 @@
 set -e
 name=$1; shift
 cd "$(dirname "$0")/../nlzm_amd/csrc"
-d=/tmp/nlzm_var_$name; mkdir -p $d
+d=$(mktemp -d); trap 'rm -rf "$d"' EXIT
 /opt/rocm/bin/hipcc "$@" -O3 -std=c++17 -fPIC --offload-arch=gfx950 -Wno-unused-function -Wno-unused-variable -c -o $d/k.o nlzm_kernels.hip &
 /opt/rocm/bin/hipcc "$@" -O3 -std=c++17 -fPIC --offload-arch=gfx950 -Wno-unused-function -Wno-unused-variable -Wno-undefined-inline -x hip -c -o $d/h.o nlzm_hip.cpp &
 wait

@@ -63,7 +63,7 @@ def test_two_rank_gather_round_trip():
 # ---- bench.py's N > 1 logic (nlzm_amd/shard.py: golden_for_rank, stream_matches, aggregate_ranks, aggregate_blocks) at world size 2 -------------------
 
 def test_golden_lookup_per_rank():
-    """bench.py --gpus N compares every rank's stream with the reference's run on that rank's block (tests/golden/gpus.json) and, at N = 1, the whole
+    """bench.py --full --gpus N compares every rank's stream with the reference's run on that rank's block (tests/golden/gpus.json) and, at N = 1, the whole
     1e9-byte stream (full.json): the lookup must find exactly those records and nothing for other sizes."""
     gd = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
     for world in (2, 4, 8):
