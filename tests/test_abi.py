@@ -82,6 +82,41 @@ def test_block_mode_placement_rule(lib):
                     assert len({seen[(st, l)] % 8 for l in range(bps)}) == 1, (nstreams, bps, st)
 
 
+OPTION_KEYS = ["workers", "worker_blocks", "hot_waves", "hot_min", "worker_threads", "block_worker_threads", "block_hot_waves",
+               "prefilter_bits_per_position", "stage_report", "parser_helper", "table_shape", "multi_allow_same_device",
+               "test_fail_launch", "test_fail_stream", "block_ext_blocks", "block_parser_helper", "keep_block_pool",
+               "block_batch_chunks", "batch_chunks", "no_such_key"]
+OPTION_VALUES = [-2, -1, 0, 1, 2, 3, 6, 7, 8, 9, 63, 64, 65, 128, 255, 256, 320, 512, 513, 576, 4096, 4097, 1 << 30, (1 << 30) + 1]
+OPTION_PROBE = """
+import json, sys
+sys.path.insert(0, sys.argv[1])
+import nlzm_amd
+lib = nlzm_amd.load_library()
+out = {}
+for call in json.loads(sys.argv[2]):
+    key, value = call.rsplit("=", 1)
+    rc = lib.nlzm_hip_set_option(key.encode(), int(value))
+    out[call] = [rc, lib.nlzm_hip_last_error().decode() if rc else ""]
+print(json.dumps(out))
+"""
+
+
+def test_set_option_keys_ranges_and_error_texts(lib):
+    """nlzm_hip_set_option needs no device: every key (and one unknown key) at and around its limits gives the return code and the
+    error text recorded in tests/golden/set_option_answers.json -- 480 calls, 277 of them accepted.  The calls are made in a child
+    process: the options are process-wide, and what is set here must not reach the tests that follow."""
+    import json
+    import sys
+    want = json.load(open(os.path.join(ROOT, "tests", "golden", "set_option_answers.json")))
+    calls = [f"{k}={v}" for k in OPTION_KEYS for v in OPTION_VALUES]
+    assert sorted(calls) == sorted(want) and len(calls) == 480
+    assert sum(1 for rc, _ in want.values() if rc == 0) == 277
+    r = subprocess.run([sys.executable, "-c", OPTION_PROBE, ROOT, json.dumps(calls)], capture_output=True, text=True)
+    assert r.returncode == 0, r.stdout + r.stderr
+    got = json.loads(r.stdout.strip().splitlines()[-1])
+    assert {c: got.get(c) for c in calls} == {c: want[c] for c in calls}
+
+
 def test_fails_loudly_without_gpu(lib):
     import torch
     if torch.cuda.is_available():
