@@ -35,6 +35,7 @@ extern "C" {
 #define NLZM_HIP_E_CAPACITY   (-4)   /* dst_cap too small                              */
 #define NLZM_HIP_E_KERNEL     (-5)   /* kernel reported an internal error / timeout    */
 #define NLZM_HIP_E_TOOBIG     (-6)   /* input >= 2^32-2^16 bytes (32-bit positions)    */
+#define NLZM_HIP_E_FORMAT     (-7)   /* not an NLZM stream / malformed / cut off       */
 
 /* Operation counters: same definitions as SURVEY.md section 8d (algorithmic bytes). */
 typedef struct nlzm_hip_stats {
@@ -208,6 +209,52 @@ int nlzm_hip_compress_blocks_multi(const int *devices, uint32_t ndev, uint32_t b
  * its block *local (0 finder, 1 table, 2 parser, 3.. workers).  With a multiple of eight streams all blocks of a stream have the
  * same workgroup index modulo 8, i.e. lie on one XCD under the round-robin dispatch (speed only). */
 void nlzm_hip_block_placement(uint32_t nstreams, uint32_t blocks_per_stream, uint32_t workgroup, uint32_t *stream, uint32_t *local);
+
+/* ---- decoding on the device: decode_file (NLZM.cpp:1912-2039), one workgroup per stream ---------------- */
+/* The streams this library writes are read back where they lie: one workgroup (a single wave) decodes one stream, the streams of a block
+ * container all at once.  The bytes accepted and produced are exactly those of the host decoder behind `nlzm d` (nlzm_amd/csrc/nlzm_host_decode.h):
+ * hist_bits 10 .. 28, frame_bits 12 .. 20, frames until the zero num_ops word.  A lone wave is an order of magnitude slower than a host core
+ * on ONE stream (DESIGN.md section 16 has the figures); the entry points are for data that is in HBM already -- verifying what was just
+ * compressed before the source is dropped, and block containers, whose streams decode beside each other.
+ * Bounds: reads stay inside [d_stream, d_stream + stream_len) -- no padding is needed behind a stream --, writes inside [d_dst, d_dst + dst_cap).
+ * A stream that is not well-formed ends with NLZM_HIP_E_FORMAT (what was decoded up to there may have been written), never with a fault; a
+ * decode that overruns a generous time bound ends with NLZM_HIP_E_KERNEL.
+ * Counters of the last call, by nlzm_hip_get_counter: "decode_syms", "decode_raw_ops", "decode_n_literal", "decode_n_dict", "decode_n_rep" (the
+ * oracle's rans_syms, bit_ops, n_literal, n_dict, n_rep), "decode_out_bytes", "decode_ring_bytes" / "decode_global_bytes" (match bytes served
+ * from the LDS ring / from memory), "decode_cycles", "decode_window_cycles", "decode_copy_cycles" (wave cycles summed over the streams: in all,
+ * waiting for input windows, copying and flushing), "decode_max_stream_cycles" and "decode_slowest_stream" (the stream with the most cycles and its index), "decode_streams", "decode_passes", "decode_ms" / "decode_us"
+ * (device time of the call's decode launches; nlzm_hip_timing stays the compress path's). */
+
+/* d_dst == NULL: size query, *dst_len = uncompressed length (the format stores none: the stream is decoded without storing).
+ * dst_cap too small: NLZM_HIP_E_CAPACITY, nothing written at or beyond d_dst + dst_cap. */
+int nlzm_hip_decompress_dev(const void *d_stream, uint64_t stream_len, void *d_dst, uint64_t dst_cap, uint64_t *dst_len);
+/* the same on host buffers (dst == NULL: size query) */
+int nlzm_hip_decompress(const uint8_t *stream, uint64_t stream_len, uint8_t *dst, uint64_t dst_cap, uint64_t *dst_len);
+
+/* nblocks streams back to back (what nlzm_hip_compress_blocks* writes).  block_len: their lengths, or NULL (found by their frame headers).
+ * raw_len_in: the blocks' uncompressed lengths where known (the .idx of `nlzm c -blocks:k` has them), else NULL (a size pass runs first).
+ * raw_len_out (may be NULL): what each block decoded to.  The blocks' bytes land in d_dst in block order, contiguous; a block that does not
+ * decode to exactly its raw_len_in is an error (NLZM_HIP_E_CAPACITY if longer, NLZM_HIP_E_FORMAT if shorter), and no block writes into
+ * another's range.  d_dst == NULL: size query (raw_len_out, *dst_len) -- by a decode without stores when raw_len_in is NULL; with raw_len_in
+ * given NOTHING is decoded and the caller's own numbers come back (their sum in *dst_len). */
+int nlzm_hip_decompress_blocks_dev(const void *d_src, uint64_t src_len, uint32_t nblocks, const uint64_t *block_len, const uint64_t *raw_len_in,
+                                   void *d_dst, uint64_t dst_cap, uint64_t *raw_len_out, uint64_t *dst_len);
+/* the same on host buffers */
+int nlzm_hip_decompress_blocks(const uint8_t *src, uint64_t src_len, uint32_t nblocks, const uint64_t *block_len, const uint64_t *raw_len_in,
+                               uint8_t *dst, uint64_t dst_cap, uint64_t *raw_len_out, uint64_t *dst_len);
+
+/* Decode (nblocks = 1: one stream) into a buffer of the library's own and compare with the n original bytes at d_orig.
+ * *decoded_len: what the stream(s) decoded to; *first_mismatch: the first offset below min(n, *decoded_len) at which the bytes differ, else
+ * that minimum (a wrong length is a mismatch at the shorter length).  EQUAL means BOTH *first_mismatch == n AND *decoded_len == n -- a stream
+ * that decodes to the n bytes and more behind them has *first_mismatch == n too, which is why the length is not optional:
+ * NLZM_HIP_VERIFY_EQUAL spells the test.  One decode pass when the blocks are the ceil(n / nblocks) partition nlzm_hip_compress_blocks*
+ * makes; any other container is sized first. */
+#define NLZM_HIP_VERIFY_EQUAL(first_mismatch, decoded_len, n) ((first_mismatch) == (n) && (decoded_len) == (n))
+int nlzm_hip_verify_dev(const void *d_src, uint64_t src_len, uint32_t nblocks, const uint64_t *block_len,
+                        const void *d_orig, uint64_t n, uint64_t *first_mismatch, uint64_t *decoded_len);
+/* the same for a caller without device pointers (`nlzm c -verify`): both buffers are uploaded first */
+int nlzm_hip_verify(const uint8_t *src, uint64_t src_len, uint32_t nblocks, const uint64_t *block_len,
+                    const uint8_t *orig, uint64_t n, uint64_t *first_mismatch, uint64_t *decoded_len);
 
 /* ---- tuning knobs (defaults are what bench.py measures) -------------------- */
 /* key: "workers" (only 1: BT4 runs on per-head worker lanes), "batch_chunks" (chunks per persistent launch), "worker_blocks" (worker CUs of a stream, default 240: the stage CUs and these fill the device),

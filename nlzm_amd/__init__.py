@@ -31,6 +31,7 @@ ABI_SYMBOLS = [
     "nlzm_hip_compress_blocks_dev", "nlzm_hip_compress_blocks", "nlzm_hip_compress_blocks_multi",
     "nlzm_hip_feed_begin", "nlzm_hip_feed", "nlzm_hip_feed_output", "nlzm_hip_feed_finish", "nlzm_hip_feed_end",
     "nlzm_hip_block_placement", "nlzm_hip_get_counter",
+    "nlzm_hip_decompress_dev", "nlzm_hip_decompress", "nlzm_hip_decompress_blocks_dev", "nlzm_hip_decompress_blocks", "nlzm_hip_verify_dev", "nlzm_hip_verify",
 ]
 
 
@@ -113,6 +114,12 @@ def load_library() -> C.CDLL:
     lib.nlzm_hip_compress_blocks_multi.argtypes = [C.POINTER(C.c_int), C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint64, C.c_uint32,
                                                    C.c_void_p, C.c_uint64, u64p, u64p]
     lib.nlzm_hip_compress_blocks_dev.argtypes = [C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint64, u64p, u64p]
+    lib.nlzm_hip_decompress_dev.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, u64p]
+    lib.nlzm_hip_decompress.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, u64p]
+    lib.nlzm_hip_decompress_blocks_dev.argtypes = [C.c_void_p, C.c_uint64, C.c_uint32, u64p, u64p, C.c_void_p, C.c_uint64, u64p, u64p]
+    lib.nlzm_hip_decompress_blocks.argtypes = [C.c_void_p, C.c_uint64, C.c_uint32, u64p, u64p, C.c_void_p, C.c_uint64, u64p, u64p]
+    lib.nlzm_hip_verify_dev.argtypes = [C.c_void_p, C.c_uint64, C.c_uint32, u64p, C.c_void_p, C.c_uint64, u64p, u64p]
+    lib.nlzm_hip_verify.argtypes = [C.c_void_p, C.c_uint64, C.c_uint32, u64p, C.c_void_p, C.c_uint64, u64p, u64p]
     _lib = lib
     return lib
 
@@ -222,6 +229,60 @@ def compress_blocks_multi(data, devices: list[int], blocks_per_dev: int, hist_bi
         pos += int(lens[i])
     assert pos == out_len.value
     return out
+
+
+def _bytes_in(data) -> np.ndarray:
+    return np.ascontiguousarray(np.frombuffer(data, dtype=np.uint8) if not isinstance(data, np.ndarray) else data)
+
+
+def decompress(stream) -> bytes:
+    """decode_file replacement on host buffers (NLZM.cpp:1912): the stream is decoded on the device, one workgroup."""
+    return b"".join(decompress_blocks(stream, 1))
+
+
+def decompress_blocks(blob, nblocks: int) -> list[bytes]:
+    """nblocks streams back to back (what compress_blocks returns, joined), decoded at once, one workgroup each."""
+    lib = load_library()
+    src = _bytes_in(blob)
+    raw = (C.c_uint64 * nblocks)()
+    total = C.c_uint64(0)
+    _chk(lib.nlzm_hip_decompress_blocks(src.ctypes.data, src.size, nblocks, None, None, None, 0, raw, C.byref(total)))
+    dst = np.empty(max(1, total.value), dtype=np.uint8)
+    _chk(lib.nlzm_hip_decompress_blocks(src.ctypes.data, src.size, nblocks, None, raw, dst.ctypes.data, total.value, raw, C.byref(total)))
+    out, pos = [], 0
+    for i in range(nblocks):
+        out.append(dst[pos: pos + int(raw[i])].tobytes())
+        pos += int(raw[i])
+    return out
+
+
+class LengthMismatch(NlzmError):
+    """verify: every byte of the original agrees, but the stream decodes to more bytes than the original has"""
+
+    def __init__(self, decoded_len: int, n: int):
+        super().__init__(f"the stream decodes to {decoded_len} bytes, the original has {n} (they agree up to there)")
+        self.decoded_len, self.n = decoded_len, n
+
+
+def verify_verdict(first: int, decoded_len: int, n: int) -> int:
+    """What verify() answers for the library's (first_mismatch, decoded_len): n when equal (NLZM_HIP_VERIFY_EQUAL), an offset below n when a
+    byte differs or the decode is shorter; a decode that is LONGER than an original it agrees with is not an offset below n and must not read
+    as n either: it raises LengthMismatch."""
+    if first == n and decoded_len == n:
+        return n
+    if first < n:
+        return first
+    raise LengthMismatch(decoded_len, n)
+
+
+def verify(blob, data, nblocks: int = 1) -> int:
+    """Decode `blob` (nblocks streams back to back) on the device and compare with `data`: the first differing offset, len(data) when equal
+    (equal: the same bytes AND the same length -- see verify_verdict)."""
+    lib = load_library()
+    src, orig = _bytes_in(blob), _bytes_in(data)
+    first, decoded = C.c_uint64(0), C.c_uint64(0)
+    _chk(lib.nlzm_hip_verify(src.ctypes.data, src.size, nblocks, None, orig.ctypes.data if orig.size else None, orig.size, C.byref(first), C.byref(decoded)))
+    return verify_verdict(int(first.value), int(decoded.value), int(orig.size))
 
 
 def stats() -> dict:

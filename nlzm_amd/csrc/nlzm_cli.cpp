@@ -15,11 +15,13 @@
 #include <string.h>
 #include <time.h>
 
+#include <exception>
 #include <thread>
 #include <string>
 #include <vector>
 
 #include "../../include/nlzm_hip.h"
+#include "nlzm_host_decode.h"
 
 namespace {
 
@@ -53,168 +55,11 @@ bool slurp(const char *path, std::vector<uint8_t> &buf)
     return ok;
 }
 
-// ---- host decoder: decode_file (NLZM.cpp:1912-2039) -----------------------------
-struct Cdf { uint16_t c[17]; };
-struct Model {
-    uint32_t rep[4];
-    Cdf cmd, lit_hi, lit_lo[16], len_direct, len_ext_hi, len_ext_lo[16], slot_hi[4], slot_lo[4][8];
-};
-void cdf_set(Cdf &d, int ns) { for (int i = 0; i <= ns; i++) d.c[i] = (uint16_t)(i * (16384 / ns)); }
-void model_init(Model &m)
-{
-    for (int i = 0; i < 4; i++) m.rep[i] = (uint32_t)i + 1;
-    cdf_set(m.cmd, 4); cdf_set(m.lit_hi, 16); cdf_set(m.len_direct, 8); cdf_set(m.len_ext_hi, 16);
-    for (int i = 0; i < 16; i++) { cdf_set(m.lit_lo[i], 16); cdf_set(m.len_ext_lo[i], 16); }
-    for (int c = 0; c < 4; c++) { cdf_set(m.slot_hi[c], 8); for (int i = 0; i < 8; i++) cdf_set(m.slot_lo[c][i], 8); }
-}
-inline void cdf_adapt(Cdf &d, int ns, int y)
-{
-    for (int i = 0; i < ns; i++) {
-        const int mix = i <= y ? i : 16384 + i + (127 - ns);                       // :284-298
-        d.c[i] = (uint16_t)(d.c[i] + ((mix - (int)d.c[i]) >> 7));                 // :348-382
-    }
-}
-inline uint32_t be32(const uint8_t *p) { return ((uint32_t)p[0] << 24) | ((uint32_t)p[1] << 16) | ((uint32_t)p[2] << 8) | p[3]; }
-
-struct Frame {
-    const uint8_t *bits, *rans, *end;
-    uint32_t word = 0, word_bits = 0, num_ops = 0, st[4], idx = 0;
-    bool bad = false;
-    int sym(Cdf &d, int nbits)                                                    // ReadCDF, :666-712
-    {
-        num_ops--;
-        uint32_t &rs = st[idx++ & 3];
-        const uint32_t f = rs & 16383u;
-        int y = 0;
-        for (int step = 1 << (nbits - 1); step; step >>= 1) y += step * (f >= d.c[y + step]);   // :388-433
-        const uint32_t start = d.c[y], freq = (uint32_t)d.c[y + 1] - start;
-        uint32_t x = freq * (rs >> 14) + f - start;                               // :457-459
-        if (x < 65536u) {                                                         // :481-488
-            if (rans + 2 > end) { bad = true; return 0; }
-            x = (x << 16) + ((uint32_t)rans[0] << 8) + rans[1];
-            rans += 2;
-        }
-        rs = x;
-        cdf_adapt(d, 1 << nbits, y);
-        return y;
-    }
-    uint32_t raw(uint32_t nb)                                                     // ReadBits, :714-731
-    {
-        num_ops--;
-        while (word_bits < 24) {
-            if (bits >= end) { bad = true; return 0; }
-            word |= (uint32_t)*bits++ << (24 - word_bits);
-            word_bits += 8;
-        }
-        const uint32_t y = word >> (32 - nb);
-        word <<= nb; word_bits -= nb;
-        return y;
-    }
-};
-inline uint32_t match_min(uint32_t d) { return 2u + (d >= 256u) + (d >= 4096u) + (d >= (1u << 20)); }   // :813-821
-inline void rep_add(uint32_t r[4], uint32_t d)
-{
-    if (r[0] == d || r[1] == d || r[2] == d || r[3] == d) return;
-    r[3] = r[2]; r[2] = r[1]; r[1] = r[0]; r[0] = d;
-}
-uint32_t dec_len(Frame &f, Model &m)                                              // model_decode_lv, :1369-1383
-{
-    uint32_t lv = (uint32_t)f.sym(m.len_direct, 3);
-    if (lv == 7) {
-        const int hi = f.sym(m.len_ext_hi, 4);
-        const int lo = f.sym(m.len_ext_lo[hi], 4);
-        lv += ((uint32_t)hi << 4) + (uint32_t)lo;
-    }
-    return lv;
-}
-
-// A byte range of the file as the decoder sees it
-struct Span {
-    const uint8_t *p; size_t n;
-    size_t size() const { return n; }
-    const uint8_t &operator[](size_t i) const { return p[i]; }
-    const uint8_t *data() const { return p; }
-};
-
-// Length of the stream that starts at in[0]: header, frames hopped over by the sizes their headers carry (:645-663),
-// terminator (:646-648).  0: malformed.  Block mode (k independent streams back to back) is split with this.
-size_t stream_length(const Span &in)
-{
-    if (in.size() < 8) return 0;
-    size_t pos = 4;
-    for (;;) {
-        if (pos + 4 > in.size()) return 0;
-        if (!be32(&in[pos])) return pos + 4;
-        if (pos + 12 > in.size()) return 0;
-        const uint32_t nb = be32(&in[pos + 4]), nr = be32(&in[pos + 8]);
-        if (nb < 12 || nr < 16 || pos + (size_t)nb + nr > in.size()) return 0;
-        pos += (size_t)nb + nr;
-    }
-}
-
-// returns 0 or a negative code; out receives the decoded bytes
-int decode_stream(const Span &in, std::vector<uint8_t> &out, uint32_t *hist_bits, uint32_t *frame_bits)
-{
-    if (in.size() < 8) return -1;
-    const uint32_t hb = ((uint32_t)in[0] << 8) + in[1], fb = ((uint32_t)in[2] << 8) + in[3];
-    *hist_bits = hb; *frame_bits = fb;
-    // the reference asserts 12 <= hist_bits (:1918) although its encoder can write 10 or 11 for
-    // inputs under 2 KiB (:1716); this decoder accepts those streams too
-    if (hb < 10 || hb > 28 || fb < 12 || fb > 20) return -2;
-    Model *m = new Model;
-    model_init(*m);
-    size_t pos = 4;
-    int rc = 0;
-    for (;;) {
-        if (pos + 4 > in.size()) { rc = -3; break; }
-        Frame f;
-        f.num_ops = be32(&in[pos]);
-        if (!f.num_ops) break;
-        if (pos + 12 > in.size()) { rc = -3; break; }
-        const uint32_t nb = be32(&in[pos + 4]), nr = be32(&in[pos + 8]);
-        if (nb < 12 || nr < 16 || pos + (size_t)nb + nr > in.size()) { rc = -3; break; }
-        f.bits = &in[pos + 12]; f.rans = &in[pos + nb]; f.end = in.data() + pos + nb + nr;
-        for (int i = 0; i < 4; i++) { f.st[i] = f.rans[0] | (f.rans[1] << 8) | (f.rans[2] << 16) | ((uint32_t)f.rans[3] << 24); f.rans += 4; }
-        while (f.num_ops > 0 && !f.bad) {
-            const int cmd = f.sym(m->cmd, 2);
-            if (cmd == 0) {
-                const int hi = f.sym(m->lit_hi, 4);
-                const int lo = f.sym(m->lit_lo[hi], 4);
-                out.push_back((uint8_t)((hi << 4) + lo));
-                continue;
-            }
-            uint32_t lv, dv;
-            if (cmd == 1) {
-                lv = dec_len(f, *m);
-                const uint32_t lc = lv < 3 ? lv : 3;
-                const int shi = f.sym(m->slot_hi[lc], 3);
-                const int slo = f.sym(m->slot_lo[lc][shi], 3);
-                dv = ((uint32_t)shi << 3) + (uint32_t)slo;
-                if (dv >= 4) {                                                    // :1395-1413
-                    uint32_t ab = (dv >> 1) - 1;
-                    dv = (2 + (dv & 1)) << ab;
-                    if (ab < 4) dv += f.raw(ab);
-                    else { ab -= 4; if (ab > 0) dv += f.raw(ab) << 4; dv += f.raw(4); }
-                }
-                dv += 1;
-            } else if (cmd == 2) {
-                const uint32_t ri = f.raw(2);
-                lv = dec_len(f, *m);
-                dv = m->rep[ri];
-            } else { rc = -5; break; }
-            lv += match_min(dv);
-            rep_add(m->rep, dv);
-            if (dv > out.size()) { rc = -6; break; }
-            const size_t from = out.size() - dv;
-            for (uint32_t i = 0; i < lv; i++) out.push_back(out[from + i]);
-        }
-        if (rc) break;
-        if (f.bad) { rc = -7; break; }
-        pos += (size_t)nb + nr;
-    }
-    delete m;
-    return rc;
-}
+// ---- host decoder: decode_file (NLZM.cpp:1912-2039), shared with the device decoder's test harness ----------
+using nlzm_host::Span;
+using nlzm_host::be32;
+using nlzm_host::stream_length;
+using nlzm_host::decode_stream;
 
 void lower(char *v) { for (; *v; v++) *v = (char)(*v | 0x20); }
 
@@ -230,6 +75,8 @@ int main(int argc, char **argv)
     uint32_t hist_bits = 22;                                                      // :2071
     uint32_t nblocks = 1;                           // -blocks:k (not in the reference): k independent streams, back to back
     uint32_t ngpus = 0;                             // -gpus:g (not in the reference): the blocks on g GPUs of this node, -blocks:k on each
+    bool verify = false;                            // -verify (not in the reference): c decodes what it wrote on the device and compares it with the input
+    bool on_gpu = false;                            // -gpu (not in the reference): d / t decode on the device; without it they are host-only and need none
     while (argc >= 2 && *argv[1] == '-') {
         char *arg = argv[1];
         argv++; argc--;
@@ -247,6 +94,10 @@ int main(int argc, char **argv)
             const int v = atoi(arg + 5);
             ngpus = (uint32_t)(v < 1 ? 1 : (v > 64 ? 64 : v));
             printf("GPUs: %d\n", ngpus);
+        } else if (!strcmp(arg, "verify")) {
+            verify = true;
+        } else if (!strcmp(arg, "gpu")) {
+            on_gpu = true;
         } else {
             printf("Unrecognized flag %s\n", arg);
             return -1;
@@ -255,7 +106,7 @@ int main(int argc, char **argv)
     const int cmd = argc >= 2 ? (argv[1][0] | 0x20) : 0;
     if (argc == 4 && cmd == 'c') {
         if (FILE *probe = fopen(argv[3], "rb")) { printf("Error: %s already exists\n", argv[3]); fclose(probe); return -1; }
-        const bool one_stream = !ngpus && nblocks == 1;
+        const bool one_stream = !ngpus && nblocks == 1 && !verify;      // (-verify needs input and stream whole: the one-call path)
         std::vector<uint8_t> in;
         FILE *fin = nullptr;
         uint64_t in_size = 0;
@@ -335,6 +186,25 @@ int main(int argc, char **argv)
         clock_gettime(CLOCK_MONOTONIC, &w1);
         (void)t0;
         if (rc) { printf("Error: %s\n", nlzm_hip_last_error()); fclose(fout); remove(argv[3]); return -1; }
+        if (verify) {
+            // the stream(s) decoded on the device, one workgroup each, and compared there with the input; neither comes back to the host
+            uint64_t first = 0, decoded = 0;
+            struct timespec v0, v1;
+            clock_gettime(CLOCK_MONOTONIC, &v0);
+            int vrc = ngpus ? nlzm_hip_init(0) : 0;
+            if (!vrc) vrc = nlzm_hip_verify(out.data(), out_n, nstreams, nstreams > 1 ? blen.data() : nullptr, in.data(), in.size(), &first, &decoded);
+            clock_gettime(CLOCK_MONOTONIC, &v1);
+            if (vrc) { printf("Error: verify: %s\n", nlzm_hip_last_error()); fclose(fout); remove(argv[3]); return -1; }
+            if (!NLZM_HIP_VERIFY_EQUAL(first, decoded, (uint64_t)in.size())) {
+                if (first < in.size() && first < decoded) printf("Verify FAILED: the stream decodes to something else from offset %" PRIu64 "; %s removed\n", first, argv[3]);
+                else printf("Verify FAILED: the stream decodes to %" PRIu64 " bytes, the input has %" PRIu64 " (equal up to offset %" PRIu64 "); %s removed\n", decoded, (uint64_t)in.size(), first, argv[3]);
+                fclose(fout); remove(argv[3]);
+                return -3;
+            }
+            uint64_t dev_us = 0;
+            (void)nlzm_hip_get_counter("decode_us", &dev_us);
+            printf("Verified (%.2f sec, %.2f of them decoding on the device)\n", (double)(v1.tv_sec - v0.tv_sec) + 1e-9 * (double)(v1.tv_nsec - v0.tv_nsec), 1e-6 * (double)dev_us);
+        }
         fwrite(out.data(), 1, (size_t)out_n, fout);
         fclose(fout);
         if (nstreams > 1) {
@@ -375,62 +245,112 @@ int main(int argc, char **argv)
         // one stream (the reference's format), or several back to back (block mode): found by hopping over the frames,
         // decoded on a host thread each, written in order
         std::vector<Span> parts;
+        std::vector<uint64_t> raws;                 // (by index) the input bytes every block holds
         size_t cut_tail = 0;
         bool by_index = false;
-        {   // the sidecar index of a block container, if it is there and fits the file: the blocks' boundaries without hopping over their frames
+        auto find_parts = [&](bool use_index) {
+            parts.clear(); raws.clear(); cut_tail = 0; by_index = false;
+            // the sidecar index of a block container, if it is there and fits the file: the blocks' boundaries without hopping over their frames
             const std::string ip = std::string(argv[2]) + ".idx";
-            if (FILE *fi = fopen(ip.c_str(), "rb")) {
+            FILE *fi = use_index ? fopen(ip.c_str(), "rb") : nullptr;
+            if (fi) {
                 unsigned ver = 0, k = 0;
                 unsigned long long n_in = 0, n_out = 0;
                 std::vector<Span> idx;
+                std::vector<uint64_t> idx_raw;
                 bool ok = fscanf(fi, "NLZMIDX %u %u %llu %llu", &ver, &k, &n_in, &n_out) == 4 && ver == 1 && k >= 1 && k <= 4096 && n_out >= in.size();
-                unsigned long long expect = 0;
+                unsigned long long expect = 0, raw_sum = 0;
                 bool cut = false;
                 for (unsigned i = 0; ok && i < k && !cut; i++) {
                     unsigned long long off = 0, len = 0, raw = 0;
-                    ok = fscanf(fi, "%llu %llu %llu", &off, &len, &raw) == 3 && off == expect && len >= 8;
-                    if (ok && off + len > in.size()) { cut = true; break; }      // (the file ends inside this block: the ones in front of it are whole)
+                    ok = fscanf(fi, "%llu %llu %llu", &off, &len, &raw) == 3 && off == expect && len >= 8 && off <= in.size() && raw <= n_in - raw_sum;
+                    if (ok && len > in.size() - off) { cut = true; break; }      // (the file ends inside this block: the ones in front of it are whole; no off + len, which can wrap)
                     // (a block's stream starts with its header and ends with its terminator, :1915-1921, :646-648)
                     if (ok) ok = in[off] == 0 && in[off + 1] >= 10 && in[off + 1] <= 28 && be32(&in[off + len - 4]) == 0;
-                    if (ok) { idx.push_back(Span{ in.data() + off, (size_t)len }); expect = off + len; }
+                    if (ok) { idx.push_back(Span{ in.data() + off, (size_t)len }); idx_raw.push_back(raw); expect = off + len; raw_sum += raw; }
                 }
                 fclose(fi);
-                if (ok && !idx.empty() && (cut || (expect == in.size() && n_out == in.size()))) {
-                    parts = idx; by_index = true;
+                if (ok && !idx.empty() && (cut || (expect == in.size() && n_out == in.size() && raw_sum == n_in))) {
+                    parts = idx; raws = idx_raw; by_index = true;
                     if (cut) cut_tail = in.size() - (size_t)expect;
                 } else printf("Note: %s does not fit this file; the blocks are found by their frame headers\n", ip.c_str());
             }
-        }
-        for (size_t pos = 0; !by_index && pos < in.size();) {
-            const Span rest{ in.data() + pos, in.size() - pos };
-            const size_t len = stream_length(rest);
-            if (!len) {
-                // what follows is not a stream: the reference stops at the first terminator (:646-648) and so do we;
-                // a container that is cut off inside its first stream is malformed
-                if (parts.empty()) break;
-                // a further stream header (:1915-1921: hist_bits, frame_bits, both big-endian 16-bit) with a frame that is cut off:
-                // the complete streams are decoded and written, and the exit status says that the container was cut
-                const bool header = rest.n >= 4 && rest.p[0] == 0 && rest.p[1] >= 10 && rest.p[1] <= 28 && rest.p[2] == 0 && rest.p[3] >= 12 && rest.p[3] <= 20;
-                if (header) cut_tail = rest.n;
-                else printf("Note: %zu bytes after the last stream ignored\n", rest.n);
-                break;
+            for (size_t pos = 0; !by_index && pos < in.size();) {
+                const Span rest{ in.data() + pos, in.size() - pos };
+                const size_t len = stream_length(rest);
+                if (!len) {
+                    // what follows is not a stream: the reference stops at the first terminator (:646-648) and so do we;
+                    // a container that is cut off inside its first stream is malformed
+                    if (parts.empty()) break;
+                    // a further stream header (:1915-1921: hist_bits, frame_bits, both big-endian 16-bit) with a frame that is cut off:
+                    // the complete streams are decoded and written, and the exit status says that the container was cut
+                    const bool header = rest.n >= 4 && rest.p[0] == 0 && rest.p[1] >= 10 && rest.p[1] <= 28 && rest.p[2] == 0 && rest.p[3] >= 12 && rest.p[3] <= 20;
+                    if (header) cut_tail = rest.n;
+                    else printf("Note: %zu bytes after the last stream ignored\n", rest.n);
+                    break;
+                }
+                parts.push_back(Span{ rest.p, len });
+                pos += len;
             }
-            parts.push_back(Span{ rest.p, len });
-            pos += len;
-        }
-        int rc = parts.empty() ? -3 : 0;
-        if (parts.size() == 1) rc = decode_stream(parts[0], out, &hb, &fb);
-        else if (!rc) {
-            std::vector<std::vector<uint8_t>> outs(parts.size());
-            std::vector<int> rcs(parts.size(), 0);
-            std::vector<uint32_t> hbs(parts.size(), 0), fbs(parts.size(), 0);
-            std::vector<std::thread> th;
-            for (size_t i = 0; i < parts.size(); i++)
-                th.emplace_back([&, i] { rcs[i] = decode_stream(parts[i], outs[i], &hbs[i], &fbs[i]); });
-            for (auto &t : th) t.join();
-            for (size_t i = 0; i < parts.size() && !rc; i++) { rc = rcs[i]; out.insert(out.end(), outs[i].begin(), outs[i].end()); }
-            hb = hbs[0]; fb = fbs[0];
-            printf("Blocks: %d\n", (int)parts.size());
+        };
+        if (on_gpu && nlzm_hip_init(0)) { printf("Error: %s\n", nlzm_hip_last_error()); if (fout) { fclose(fout); remove(argv[3]); } return -1; }
+        int rc = 0;
+        for (int attempt = 0; attempt < 2; attempt++) {
+            find_parts(attempt == 0);
+            out.clear();
+            rc = parts.empty() ? -3 : 0;
+            bool index_wrong = false;               // a block did not decode to the bytes its index entry says it holds
+            if (!rc && on_gpu) {
+                // all blocks at once on the device, one workgroup each; boundaries from above, raw lengths from the index where it gave them
+                std::vector<uint64_t> blen(parts.size()), raw(parts.size());
+                for (size_t i = 0; i < parts.size(); i++) blen[i] = parts[i].n;
+                const uint64_t src_len = (uint64_t)(parts.back().p + parts.back().n - parts[0].p);
+                uint64_t total = 0;
+                int drc = 0;
+                if (by_index) {
+                    // the index says what every block holds: one decode pass, every block bounded by its entry -- a block that decodes to more
+                    // (NLZM_HIP_E_CAPACITY) or to less (NLZM_HIP_E_FORMAT) than that shows the index to be wrong, and the frame headers decide
+                    // (the sizes are the index's word and nothing else yet: an index that asks for more memory than the host or the device has is a
+                    //  wrong index, not a reason to die)
+                    for (size_t i = 0; i < parts.size(); i++) total += raws[i];
+                    bool room = true;
+                    try { out.resize((size_t)total); } catch (const std::exception &) { room = false; }
+                    if (room) drc = nlzm_hip_decompress_blocks(parts[0].p, src_len, (uint32_t)parts.size(), blen.data(), raws.data(), out.data(), total, raw.data(), &total);
+                    if (!room || drc == NLZM_HIP_E_CAPACITY || drc == NLZM_HIP_E_FORMAT || drc == NLZM_HIP_E_NOMEM) { index_wrong = true; drc = 0; std::vector<uint8_t>().swap(out); }
+                } else {
+                    // no lengths anywhere in the format: a size pass, then the decode
+                    drc = nlzm_hip_decompress_blocks(parts[0].p, src_len, (uint32_t)parts.size(), blen.data(), nullptr, nullptr, 0, raw.data(), &total);
+                    if (!drc) {
+                        out.resize((size_t)total);
+                        drc = nlzm_hip_decompress_blocks(parts[0].p, src_len, (uint32_t)parts.size(), blen.data(), raw.data(), out.data(), total, nullptr, &total);
+                    }
+                }
+                if (drc == NLZM_HIP_E_FORMAT) rc = -7;
+                else if (drc) { printf("Error: %s\n", nlzm_hip_last_error()); if (fout) { fclose(fout); remove(argv[3]); } return -1; }
+                hb = parts[0].p[1]; fb = parts[0].p[3];
+                if (parts.size() > 1) printf("Blocks: %d\n", (int)parts.size());
+            } else if (parts.size() == 1) {
+                rc = decode_stream(parts[0], out, &hb, &fb);
+                if (!rc && by_index && out.size() != raws[0]) index_wrong = true;
+            } else if (!rc) {
+                std::vector<std::vector<uint8_t>> outs(parts.size());
+                std::vector<int> rcs(parts.size(), 0);
+                std::vector<uint32_t> hbs(parts.size(), 0), fbs(parts.size(), 0);
+                std::vector<std::thread> th;
+                for (size_t i = 0; i < parts.size(); i++)
+                    th.emplace_back([&, i] { rcs[i] = decode_stream(parts[i], outs[i], &hbs[i], &fbs[i]); });
+                for (auto &t : th) t.join();
+                for (size_t i = 0; i < parts.size() && !rc; i++) {
+                    rc = rcs[i];
+                    if (!rc && by_index && outs[i].size() != raws[i]) index_wrong = true;
+                    out.insert(out.end(), outs[i].begin(), outs[i].end());
+                }
+                hb = hbs[0]; fb = fbs[0];
+                if (!index_wrong) printf("Blocks: %d\n", (int)parts.size());
+            }
+            if (!(by_index && (index_wrong || rc))) break;
+            // the index passed its checks and still does not describe these streams (stale, or of another file): the frame headers decide
+            printf("Note: %s.idx does not describe this file's blocks; they are found by their frame headers\n", argv[2]);
         }
         if (rc) { printf("Assert failed: malformed stream (%d)\n", rc); if (fout) fclose(fout); return -1; }
         printf("Dictionary: %d KB\n", (int)(((1ull << hb) + 1023) >> 10));
@@ -452,7 +372,10 @@ int main(int argc, char **argv)
                "Flags:\n"
                "\t-window:bits = Maximum window size in bits, default 22 (4 MB), min 15, max 28 (32 KB to 256 MB)\n"
                "\t-blocks:k = (this build) compress k independent blocks at once; d/t read the streams back to back\n"
-               "\t-gpus:g = (this build) the blocks on GPUs 0..g-1 of this node, -blocks:k of them on each\n");
+               "\t-gpus:g = (this build) the blocks on GPUs 0..g-1 of this node, -blocks:k of them on each\n"
+               "\t-verify = (this build) c decodes what it wrote on the GPU, one workgroup per stream, compares it with the input\n"
+               "\t          and removes the output if they differ\n"
+               "\t-gpu = (this build) d / t decode on the GPU, all blocks of a container at once (without it they run on the host)\n");
     }
     return 0;
 }

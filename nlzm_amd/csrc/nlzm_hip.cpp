@@ -897,6 +897,19 @@ int stream_finish(Ctx &C, uint64_t *dst_len, bool report)
 
 }  // namespace
 
+// ---- what the decoder's entry points (nlzm_hip_decode.cpp) use of this file's state: the error text, the library's stream ----
+namespace nlzm {
+int host_error(int code, const char *text) { return set_err(code, "%s", text); }
+int host_stream(hipStream_t *st)
+{
+    Ctx &C = cur().ctx;
+    if (!C.inited) return set_err(NLZM_HIP_E_NODEVICE, "nlzm_hip_init() has not succeeded (no device: there is no CPU fallback)");
+    *st = C.st;
+    return 0;
+}
+int decode_counter(const char *key, uint64_t *value);      // "decode_*": nlzm_hip_decode.cpp
+}  // namespace nlzm
+
 extern "C" {
 
 static void dev_shutdown(DevState &D);
@@ -1056,6 +1069,7 @@ int nlzm_hip_get_counter(const char *key, uint64_t *value)
     DevState &D = cur();
     Ctx &C = D.ctx;
     if (!key || !value) return set_err(NLZM_HIP_E_ARG, "null argument");
+    if (!strncmp(key, "decode_", 7)) return nlzm::decode_counter(key, value);
     if (C.open) { const int rc = refresh_stats(C, D.opt.report != 0); if (rc) return rc; }
     static const struct { const char *name; int idx; } kProf[] = {
         { "finder_blocks", 0 }, { "table_blocks", 6 }, { "parser_blocks", 8 }, { "parser_passes", 13 },

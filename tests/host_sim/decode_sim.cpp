@@ -1,0 +1,263 @@
+// decode_sim.cpp -- the decoder role (nlzm_amd/csrc/nlzm_decode.h) run on the CPU, every lane a fiber (xw_sim.cpp), beside the
+// host decoder (nlzm_amd/csrc/nlzm_host_decode.h), which is the specification.  TEST HARNESS ONLY (tests/test_decode_sim.py).
+//
+//   decode_sim decode  <stream> <out> [size]        one stream; `size`: nothing is stored, only the length found
+//   decode_sim blocks  <container> <out> <given>    k streams back to back as k workgroups of one launch; given = 1: block and raw
+//                                                   lengths from the host decoder, 0: split by frame hopping + a size-only launch first
+//   decode_sim mutants <stream> <seed> <flips> <shard> <nshards>    damaged copies of the stream: role and host decoder must agree
+//
+// Every buffer the role sees lies between two canary regions, at an address that is deliberately not aligned; the canaries are
+// checked after every launch.
+#define NLZM_SIM 1
+#include "../../nlzm_amd/csrc/nlzm_decode.h"
+#include "../../nlzm_amd/csrc/nlzm_host_decode.h"
+
+#include <stdio.h>
+#include <stdlib.h>
+#include <string.h>
+
+#include <map>
+#include <string>
+#include <vector>
+
+using namespace nlzm;
+
+namespace {
+
+constexpr size_t kCanary = 4096;
+constexpr uint8_t kPoison = 0xA5;
+
+// a buffer of n bytes at a chosen misalignment between two canaries
+struct Guarded {
+    std::vector<uint8_t> mem;
+    size_t off = 0, n = 0;
+    void make(size_t bytes, size_t misalign, uint8_t fill)
+    {
+        n = bytes;
+        mem.assign(2 * kCanary + bytes + 64, kPoison);
+        off = kCanary + ((64 - ((uintptr_t)mem.data() + kCanary) % 64) % 64) + misalign;
+        memset(mem.data() + off, fill, bytes);
+    }
+    uint8_t *p() { return mem.data() + off; }
+    bool intact() const
+    {
+        for (size_t i = 0; i < off; i++) if (mem[i] != kPoison) return false;
+        for (size_t i = off + n; i < mem.size(); i++) if (mem[i] != kPoison) return false;
+        return true;
+    }
+};
+
+std::vector<uint8_t> slurp(const char *path)
+{
+    std::vector<uint8_t> b;
+    FILE *f = fopen(path, "rb");
+    if (!f) { fprintf(stderr, "cannot read %s\n", path); exit(2); }
+    fseek(f, 0, SEEK_END); const long sz = ftell(f); fseek(f, 0, SEEK_SET);
+    b.resize((size_t)sz);
+    if (sz && fread(b.data(), 1, (size_t)sz, f) != (size_t)sz) { fprintf(stderr, "short read\n"); exit(2); }
+    fclose(f);
+    return b;
+}
+void spill(const char *path, const uint8_t *p, size_t n)
+{
+    FILE *f = fopen(path, "wb");
+    if (!f) { fprintf(stderr, "cannot write %s\n", path); exit(2); }
+    if (n) fwrite(p, 1, n, f);
+    fclose(f);
+}
+
+struct LaunchPack { std::vector<dec::StreamArgs> a; std::vector<dec::StreamResult> r; };
+void entry(void *arg)
+{
+    LaunchPack *P = (LaunchPack *)arg;
+    const uint32_t b = xw::block_index();
+    dec::decode_role(P->a[b], &P->r[b]);
+}
+void run(LaunchPack &P)
+{
+    P.r.assign(P.a.size(), dec::StreamResult{});
+    std::vector<unsigned long long> lds(P.a.size(), sizeof(dec::Lds));
+    xw::launch((uint32_t)P.a.size(), 64, lds.data(), entry, &P);
+}
+
+void print_result(const dec::StreamResult &r)
+{
+    printf("rc=%d detail=%u out_len=%llu syms=%llu raw_ops=%llu n_literal=%llu n_dict=%llu n_rep=%llu ring_bytes=%llu global_bytes=%llu\n", r.rc, r.detail,
+           r.out_len, r.syms, r.raw_ops, r.n_literal, r.n_dict, r.n_rep, r.ring_bytes, r.global_bytes);
+}
+
+int cmd_decode(int argc, char **argv)
+{
+    const std::vector<uint8_t> stream = slurp(argv[2]);
+    const bool size_only = argc > 4 && !strcmp(argv[4], "size");
+    std::vector<uint8_t> want;
+    uint32_t hb = 0, fb = 0;
+    nlzm_host::Counts hc;
+    nlzm_host::MatchLog log;
+    const int hrc = nlzm_host::decode_stream(nlzm_host::Span{ stream.data(), stream.size() }, want, &hb, &fb, &hc, &log);
+    printf("ring=%u reach=%u flush=%u\n", dec::kRing, dec::kRing, dec::kFlush);
+    printf("host rc=%d out_len=%zu syms=%llu raw_ops=%llu n_literal=%llu n_dict=%llu n_rep=%llu\n", hrc, want.size(), (unsigned long long)hc.syms,
+           (unsigned long long)hc.raw_ops, (unsigned long long)hc.n_literal, (unsigned long long)hc.n_dict, (unsigned long long)hc.n_rep);
+    {   // (distance, length) histogram of the matches longer than 64
+        std::map<std::pair<uint32_t, uint32_t>, uint32_t> h;
+        for (size_t i = 0; i < log.dv.size(); i++) if (log.lv[i] > 64) h[{ log.dv[i], log.lv[i] }]++;
+        size_t shown = 0;
+        for (const auto &e : h) { if (shown++ >= 4000) break; printf("longmatch %u %u %u\n", e.first.first, e.first.second, e.second); }
+    }
+    Guarded src, dst;
+    src.make(stream.size(), 1, 0);
+    memcpy(src.p(), stream.data(), stream.size());
+    dst.make(want.size(), 3, 0x5C);                 // (size only: must stay 0x5C)
+    LaunchPack P;
+    P.a.push_back(dec::StreamArgs{ src.p(), stream.size(), size_only ? nullptr : dst.p(), size_only ? ~0ull : want.size(), ~0ull });
+    run(P);
+    print_result(P.r[0]);
+    if (!src.intact() || !dst.intact()) { printf("FAIL: canary damaged\n"); return 1; }
+    const dec::StreamResult &r = P.r[0];
+    if ((r.rc != 0) != (hrc != 0)) { printf("FAIL: role rc %d, host decoder rc %d\n", r.rc, hrc); return 1; }
+    if (!hrc) {
+        if (r.out_len != want.size()) { printf("FAIL: length\n"); return 1; }
+        if (r.syms != hc.syms || r.raw_ops != hc.raw_ops || r.n_literal != hc.n_literal || r.n_dict != hc.n_dict || r.n_rep != hc.n_rep) { printf("FAIL: counters\n"); return 1; }
+        unsigned long long want_ring = 0, want_global = 0;      // what the parse says each side serves (nlzm_decode.h, copy)
+        for (size_t i = 0; i < log.dv.size(); i++)
+            (log.dv[i] + (log.dv[i] < log.lv[i] ? log.lv[i] : 0u) <= dec::kRing ? want_ring : want_global) += log.lv[i];
+        if (!size_only && (r.ring_bytes != want_ring || r.global_bytes != want_global)) { printf("FAIL: ring / memory byte counters\n"); return 1; }
+        if (size_only) {
+            for (size_t i = 0; i < want.size(); i++) if (dst.p()[i] != 0x5C) { printf("FAIL: size-only mode wrote\n"); return 1; }
+        } else if (want.size() && memcmp(dst.p(), want.data(), want.size())) { printf("FAIL: bytes differ from the host decoder's\n"); return 1; }
+    }
+    if (!size_only) spill(argv[3], dst.p(), hrc ? 0 : want.size());
+    printf("decode_sim: OK\n");
+    return 0;
+}
+
+int cmd_blocks(int argc, char **argv)
+{
+    (void)argc;
+    const std::vector<uint8_t> blob = slurp(argv[2]);
+    const bool given = atoi(argv[4]) != 0;
+    Guarded src;
+    src.make(blob.size(), 2, 0);
+    memcpy(src.p(), blob.data(), blob.size());
+    std::vector<size_t> off, len, raw;
+    for (size_t pos = 0; pos < blob.size();) {      // the container's split: what the library's hop over the frame headers does
+        const size_t l = nlzm_host::stream_length(nlzm_host::Span{ blob.data() + pos, blob.size() - pos });
+        if (!l) { printf("FAIL: container does not split\n"); return 1; }
+        off.push_back(pos); len.push_back(l); pos += l;
+    }
+    const size_t k = off.size();
+    std::vector<uint8_t> want;
+    for (size_t i = 0; i < k; i++) {
+        std::vector<uint8_t> o; uint32_t hb, fb;
+        if (nlzm_host::decode_stream(nlzm_host::Span{ blob.data() + off[i], len[i] }, o, &hb, &fb)) { printf("FAIL: host decoder rejects block %zu\n", i); return 1; }
+        raw.push_back(o.size());
+        want.insert(want.end(), o.begin(), o.end());
+    }
+    std::vector<size_t> got_raw = raw;
+    if (!given) {                                   // raw lengths unknown: a size-only launch of all blocks first
+        LaunchPack Z;
+        for (size_t i = 0; i < k; i++) Z.a.push_back(dec::StreamArgs{ src.p() + off[i], len[i], nullptr, ~0ull, ~0ull });
+        run(Z);
+        for (size_t i = 0; i < k; i++) { if (Z.r[i].rc) { printf("FAIL: size pass rc %d\n", Z.r[i].rc); return 1; } got_raw[i] = (size_t)Z.r[i].out_len; }
+    }
+    size_t total = 0;
+    for (size_t i = 0; i < k; i++) total += got_raw[i];
+    Guarded dst;
+    dst.make(total, 5, 0x5C);
+    LaunchPack P;
+    size_t at = 0;
+    for (size_t i = 0; i < k; i++) { P.a.push_back(dec::StreamArgs{ src.p() + off[i], len[i], dst.p() + at, got_raw[i], ~0ull }); at += got_raw[i]; }
+    run(P);
+    printf("blocks=%zu raw_len_out=", k);
+    for (size_t i = 0; i < k; i++) printf("%s%llu", i ? "," : "", P.r[i].out_len);
+    printf("\n");
+    for (size_t i = 0; i < k; i++) if (P.r[i].rc || P.r[i].out_len != raw[i]) { printf("FAIL: block %zu rc %d\n", i, P.r[i].rc); return 1; }
+    if (!src.intact() || !dst.intact()) { printf("FAIL: canary damaged\n"); return 1; }
+    if (total != want.size() || memcmp(dst.p(), want.data(), total)) { printf("FAIL: bytes differ\n"); return 1; }
+    spill(argv[3], dst.p(), total);
+    printf("decode_sim: OK\n");
+    return 0;
+}
+
+// one damaged stream through both decoders; returns 0 when they agree
+int one_mutant(const std::vector<uint8_t> &s, const char *what, size_t idx, long long cap_delta, unsigned *accepted)
+{
+    std::vector<uint8_t> want;
+    uint32_t hb = 0, fb = 0;
+    const int hrc = nlzm_host::decode_stream(nlzm_host::Span{ s.data(), s.size() }, want, &hb, &fb);
+    Guarded src, dst;
+    src.make(s.size(), idx % 4, 0);
+    if (s.size()) memcpy(src.p(), s.data(), s.size());
+    const size_t cap = (size_t)((long long)want.size() + cap_delta);
+    dst.make(cap, idx % 16, 0x5C);
+    LaunchPack P;
+    P.a.push_back(dec::StreamArgs{ src.p(), s.size(), dst.p(), cap, ~0ull });
+    run(P);
+    const dec::StreamResult &r = P.r[0];
+    if (!src.intact() || !dst.intact()) { printf("FAIL %s %zu: canary damaged\n", what, idx); return 1; }
+    if (cap_delta < 0) {
+        if (hrc || r.rc != dec::kErrCapacity) { printf("FAIL %s %zu: dst_cap one short gives rc %d\n", what, idx, r.rc); return 1; }
+        return 0;
+    }
+    if ((r.rc != 0) != (hrc != 0)) { printf("FAIL %s %zu: role rc %d (detail %u), host decoder rc %d\n", what, idx, r.rc, r.detail, hrc); return 1; }
+    if (!hrc) {
+        (*accepted)++;
+        if (r.out_len != want.size() || (want.size() && memcmp(dst.p(), want.data(), want.size()))) { printf("FAIL %s %zu: accepted, bytes differ\n", what, idx); return 1; }
+    }
+    return 0;
+}
+
+uint32_t rng_state;
+uint32_t rnd() { rng_state = rng_state * 1664525u + 1013904223u; return rng_state >> 8; }
+void put_be32(std::vector<uint8_t> &s, size_t at, uint32_t v) { s[at] = (uint8_t)(v >> 24); s[at + 1] = (uint8_t)(v >> 16); s[at + 2] = (uint8_t)(v >> 8); s[at + 3] = (uint8_t)v; }
+
+int cmd_mutants(int argc, char **argv)
+{
+    (void)argc;
+    const std::vector<uint8_t> s0 = slurp(argv[2]);
+    rng_state = (uint32_t)strtoul(argv[3], nullptr, 10);
+    const size_t flips = (size_t)atoi(argv[4]), shard = (size_t)atoi(argv[5]), nshards = (size_t)atoi(argv[6]);
+    // the list is made whole in every shard (same seed), each runs its share
+    struct Mut { std::string what; std::vector<uint8_t> s; long long cap_delta; };
+    std::vector<Mut> muts;
+    const uint32_t nb0 = s0.size() >= 16 ? nlzm_host::be32(&s0[8]) : 12;
+    const size_t head = s0.size() < 64 ? s0.size() : (size_t)(4 + nb0 + 16 < s0.size() ? 4 + nb0 + 16 : s0.size());      // header, first frame's header ... states
+    for (size_t i = 0; i < flips; i++) {
+        Mut m{ "flip", s0, 0 };
+        size_t at;
+        if (i % 2 == 0) { at = rnd() % (head < 32 ? head : 32); if (i % 4 == 0 && head > 32) at = 4 + nb0 + rnd() % 16; }   // frame header / states
+        else at = rnd() % s0.size();
+        if (at >= s0.size()) at = s0.size() - 1;
+        m.s[at] ^= (uint8_t)(1u << (rnd() % 8));
+        muts.push_back(m);
+    }
+    for (size_t c = 1; c <= 16 && c <= s0.size(); c++) { Mut m{ "cut", s0, 0 }; m.s.resize(s0.size() - c); muts.push_back(m); }
+    for (int v : { 9, 29 }) { Mut m{ "hist_bits", s0, 0 }; m.s[0] = 0; m.s[1] = (uint8_t)v; muts.push_back(m); }
+    for (int v : { 11, 21 }) { Mut m{ "frame_bits", s0, 0 }; m.s[2] = 0; m.s[3] = (uint8_t)v; muts.push_back(m); }
+    if (s0.size() >= 16) {
+        const uint32_t ops = nlzm_host::be32(&s0[4]);
+        { Mut m{ "nb", s0, 0 }; put_be32(m.s, 8, 11); muts.push_back(m); }
+        { Mut m{ "nr", s0, 0 }; put_be32(m.s, 12, 15); muts.push_back(m); }
+        for (uint32_t v : { ops + 1, ops - 1, 0xFFFFFFFFu }) { Mut m{ "num_ops", s0, 0 }; put_be32(m.s, 4, v); muts.push_back(m); }
+    }
+    muts.push_back(Mut{ "cap", s0, -1 });
+    unsigned accepted = 0, ran = 0;
+    for (size_t i = shard; i < muts.size(); i += nshards) {
+        if (one_mutant(muts[i].s, muts[i].what.c_str(), i, muts[i].cap_delta, &accepted)) return 1;
+        ran++;
+    }
+    printf("mutants=%zu ran=%u accepted=%u\n", muts.size(), ran, accepted);
+    printf("decode_sim: OK\n");
+    return 0;
+}
+
+}  // namespace
+
+int main(int argc, char **argv)
+{
+    if (argc >= 4 && !strcmp(argv[1], "decode")) return cmd_decode(argc, argv);
+    if (argc == 5 && !strcmp(argv[1], "blocks")) return cmd_blocks(argc, argv);
+    if (argc == 7 && !strcmp(argv[1], "mutants")) return cmd_mutants(argc, argv);
+    fprintf(stderr, "usage: see the head of decode_sim.cpp\n");
+    return 2;
+}
