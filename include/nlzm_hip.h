@@ -256,6 +256,35 @@ int nlzm_hip_verify_dev(const void *d_src, uint64_t src_len, uint32_t nblocks, c
 int nlzm_hip_verify(const uint8_t *src, uint64_t src_len, uint32_t nblocks, const uint64_t *block_len,
                     const uint8_t *orig, uint64_t n, uint64_t *first_mismatch, uint64_t *decoded_len);
 
+/* ---- CRC32 of bytes in device memory, and checking a container without its original ------------------------ */
+/* The CRC is the reference's crc32_calc (NLZM.cpp:126-199): reflected polynomial 0xEDB88320, init and final xor 0xFFFFFFFF -- zlib.crc32, and what
+ * `nlzm h` prints.  The format stores none; `nlzm c -crc` keeps one per block in the sidecar index (NLZMIDX 2).  A range is cut into segments of
+ * nlzm_hip_get_counter("crc_segment_bytes") bytes, one wave each, whose results are combined on the device, always in the same order.
+ * Bounds: reads stay inside [d_buf + off, d_buf + off + len) of every range -- no padding, no alignment is asked for.  `seed` chains calls as
+ * zlib.crc32(b, seed) does.  Counters of the last call: "crc_us" (device time of its CRC launches), "crc_bytes", "crc_segment_bytes" (needs no device). */
+int nlzm_hip_crc32_dev(const void *d_buf, uint64_t n, uint32_t seed, uint32_t *crc);
+int nlzm_hip_crc32(const uint8_t *buf, uint64_t n, uint32_t seed, uint32_t *crc);          /* uploads first */
+/* nranges ranges of one buffer in one call (seed 0): they may be empty, overlap and be unaligned; a range with off + len > buf_len is
+ * NLZM_HIP_E_ARG.  off / len / crc: host arrays of nranges entries. */
+int nlzm_hip_crc32_ranges_dev(const void *d_buf, uint64_t buf_len, uint32_t nranges,
+                              const uint64_t *off, const uint64_t *len, uint32_t *crc);
+int nlzm_hip_crc32_ranges(const uint8_t *buf, uint64_t buf_len, uint32_t nranges,
+                          const uint64_t *off, const uint64_t *len, uint32_t *crc);         /* uploads first (the command line holds no device pointers) */
+/* CRC32 of A || B from crc_a = CRC32 of A, crc_b = CRC32 of B and len_b = |B| (zlib's crc32_combine).  A pure function: it needs no device, cannot
+ * fail and returns the CRC itself. */
+uint32_t nlzm_hip_crc32_combine(uint32_t crc_a, uint32_t crc_b, uint64_t len_b);
+/* between feed_finish and feed_end: CRC32 of the fed input, which is whole in HBM */
+int nlzm_hip_feed_input_crc32(uint32_t *crc);
+
+/* Decode (as nlzm_hip_verify_dev does, into a buffer of the library's own) and compare every block's CRC32 and length with what the
+ * caller holds -- the original is not needed.  raw_len may be NULL (a size pass runs first; then only the CRCs are checked).
+ * *first_bad: index of the first block whose decoded length or CRC32 differs, nblocks when none does.  crc_out (may be NULL): what each
+ * block's bytes hash to.  A stream that is not well-formed is NLZM_HIP_E_FORMAT as everywhere else. */
+int nlzm_hip_check_dev(const void *d_src, uint64_t src_len, uint32_t nblocks, const uint64_t *block_len, const uint64_t *raw_len,
+                       const uint32_t *crc, uint32_t *first_bad, uint32_t *crc_out);
+int nlzm_hip_check(const uint8_t *src, uint64_t src_len, uint32_t nblocks, const uint64_t *block_len, const uint64_t *raw_len,
+                   const uint32_t *crc, uint32_t *first_bad, uint32_t *crc_out);
+
 /* ---- tuning knobs (defaults are what bench.py measures) -------------------- */
 /* key: "workers" (only 1: BT4 runs on per-head worker lanes), "batch_chunks" (chunks per persistent launch), "worker_blocks" (worker CUs of a stream, default 240: the stage CUs and these fill the device),
  * "worker_threads" (bin-taking lanes per worker CU, 64..512, default 128), "hot_waves" (waves per worker CU that take a hot

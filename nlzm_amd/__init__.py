@@ -32,6 +32,8 @@ ABI_SYMBOLS = [
     "nlzm_hip_feed_begin", "nlzm_hip_feed", "nlzm_hip_feed_output", "nlzm_hip_feed_finish", "nlzm_hip_feed_end",
     "nlzm_hip_block_placement", "nlzm_hip_get_counter",
     "nlzm_hip_decompress_dev", "nlzm_hip_decompress", "nlzm_hip_decompress_blocks_dev", "nlzm_hip_decompress_blocks", "nlzm_hip_verify_dev", "nlzm_hip_verify",
+    "nlzm_hip_crc32_dev", "nlzm_hip_crc32", "nlzm_hip_crc32_ranges_dev", "nlzm_hip_crc32_ranges", "nlzm_hip_crc32_combine", "nlzm_hip_feed_input_crc32",
+    "nlzm_hip_check_dev", "nlzm_hip_check",
 ]
 
 
@@ -120,6 +122,15 @@ def load_library() -> C.CDLL:
     lib.nlzm_hip_decompress_blocks.argtypes = [C.c_void_p, C.c_uint64, C.c_uint32, u64p, u64p, C.c_void_p, C.c_uint64, u64p, u64p]
     lib.nlzm_hip_verify_dev.argtypes = [C.c_void_p, C.c_uint64, C.c_uint32, u64p, C.c_void_p, C.c_uint64, u64p, u64p]
     lib.nlzm_hip_verify.argtypes = [C.c_void_p, C.c_uint64, C.c_uint32, u64p, C.c_void_p, C.c_uint64, u64p, u64p]
+    lib.nlzm_hip_crc32_dev.argtypes = [C.c_void_p, C.c_uint64, C.c_uint32, u32p]
+    lib.nlzm_hip_crc32.argtypes = [C.c_void_p, C.c_uint64, C.c_uint32, u32p]
+    lib.nlzm_hip_crc32_ranges_dev.argtypes = [C.c_void_p, C.c_uint64, C.c_uint32, u64p, u64p, u32p]
+    lib.nlzm_hip_crc32_ranges.argtypes = [C.c_void_p, C.c_uint64, C.c_uint32, u64p, u64p, u32p]
+    lib.nlzm_hip_crc32_combine.argtypes = [C.c_uint32, C.c_uint32, C.c_uint64]
+    lib.nlzm_hip_crc32_combine.restype = C.c_uint32
+    lib.nlzm_hip_feed_input_crc32.argtypes = [u32p]
+    lib.nlzm_hip_check_dev.argtypes = [C.c_void_p, C.c_uint64, C.c_uint32, u64p, u64p, u32p, u32p, u32p]
+    lib.nlzm_hip_check.argtypes = [C.c_void_p, C.c_uint64, C.c_uint32, u64p, u64p, u32p, u32p, u32p]
     _lib = lib
     return lib
 
@@ -283,6 +294,44 @@ def verify(blob, data, nblocks: int = 1) -> int:
     first, decoded = C.c_uint64(0), C.c_uint64(0)
     _chk(lib.nlzm_hip_verify(src.ctypes.data, src.size, nblocks, None, orig.ctypes.data if orig.size else None, orig.size, C.byref(first), C.byref(decoded)))
     return verify_verdict(int(first.value), int(decoded.value), int(orig.size))
+
+
+def crc32(data, seed: int = 0) -> int:
+    """CRC32 (zlib.crc32's, the reference's crc32_calc) of `data`, uploaded and hashed on the device; `seed` chains calls as zlib's does."""
+    lib = load_library()
+    src = _bytes_in(data)
+    out = C.c_uint32(0)
+    _chk(lib.nlzm_hip_crc32(src.ctypes.data if src.size else None, src.size, seed & 0xFFFFFFFF, C.byref(out)))
+    return int(out.value)
+
+
+def crc32_ranges(data, ranges) -> list[int]:
+    """The CRC32 of every (offset, length) range of `data`, all in one call on the device; the ranges may be empty and may overlap."""
+    lib = load_library()
+    src = _bytes_in(data)
+    k = len(ranges)
+    off, ln, out = (C.c_uint64 * max(1, k))(*[int(o) for o, _ in ranges]), (C.c_uint64 * max(1, k))(*[int(l) for _, l in ranges]), (C.c_uint32 * max(1, k))()
+    _chk(lib.nlzm_hip_crc32_ranges(src.ctypes.data if src.size else None, src.size, k, off, ln, out))
+    return [int(out[i]) for i in range(k)]
+
+
+def crc32_combine(a: int, b: int, len_b: int) -> int:
+    """CRC32 of A + B from crc32(A), crc32(B) and len(B) (zlib's crc32_combine); needs no device."""
+    return int(load_library().nlzm_hip_crc32_combine(a & 0xFFFFFFFF, b & 0xFFFFFFFF, len_b))
+
+
+def check(blob, crcs, nblocks: int = 1, raw_lens=None) -> int:
+    """Decode `blob` (nblocks streams back to back) on the device and compare every block's CRC32 -- and its length, where raw_lens gives
+    them -- with what the caller holds; the original is not needed.  The first bad block, nblocks when none is."""
+    lib = load_library()
+    src = _bytes_in(blob)
+    if len(crcs) != nblocks or (raw_lens is not None and len(raw_lens) != nblocks):
+        raise ValueError("one CRC (and one length) per block")
+    want = (C.c_uint32 * nblocks)(*[int(c) & 0xFFFFFFFF for c in crcs])
+    raw = (C.c_uint64 * nblocks)(*[int(r) for r in raw_lens]) if raw_lens is not None else None
+    bad = C.c_uint32(0)
+    _chk(lib.nlzm_hip_check(src.ctypes.data, src.size, nblocks, None, raw, want, C.byref(bad), None))
+    return int(bad.value)
 
 
 def stats() -> dict:

@@ -76,6 +76,7 @@ int main(int argc, char **argv)
     uint32_t nblocks = 1;                           // -blocks:k (not in the reference): k independent streams, back to back
     uint32_t ngpus = 0;                             // -gpus:g (not in the reference): the blocks on g GPUs of this node, -blocks:k on each
     bool verify = false;                            // -verify (not in the reference): c decodes what it wrote on the device and compares it with the input
+    bool with_crc = false;                          // -crc (not in the reference): c keeps every block's CRC32, hashed on the device, in the index (NLZMIDX 2); d / t check them
     bool on_gpu = false;                            // -gpu (not in the reference): d / t decode on the device; without it they are host-only and need none
     while (argc >= 2 && *argv[1] == '-') {
         char *arg = argv[1];
@@ -96,6 +97,8 @@ int main(int argc, char **argv)
             printf("GPUs: %d\n", ngpus);
         } else if (!strcmp(arg, "verify")) {
             verify = true;
+        } else if (!strcmp(arg, "crc")) {
+            with_crc = true;
         } else if (!strcmp(arg, "gpu")) {
             on_gpu = true;
         } else {
@@ -157,7 +160,7 @@ int main(int argc, char **argv)
             for (uint64_t done = 0; !rc && done < in_size;) {
                 const size_t m = (size_t)(in_size - done < piece.size() ? in_size - done : piece.size());
                 if (fread(piece.data(), 1, m, fin) != m) { printf("Error: %s could not be read\n", argv[2]); rc = -1; break; }
-                crc = crc_calc(piece.data(), m, crc);
+                if (!with_crc) crc = crc_calc(piece.data(), m, crc);
                 rc = nlzm_hip_feed(piece.data(), m);
                 done += m;
                 drain();
@@ -166,11 +169,20 @@ int main(int argc, char **argv)
             }
             if (!rc) rc = nlzm_hip_feed_finish();
             drain();
+            if (!rc && with_crc) rc = nlzm_hip_feed_input_crc32(&crc);      // (the input is whole in HBM and nowhere on the host: hashed where it lies)
             nlzm_hip_feed_end();
             fclose(fin);
             clock_gettime(CLOCK_MONOTONIC, &w1);
             if (rc) { if (rc != -1) printf("Error: %s\n", nlzm_hip_last_error()); fclose(fout); remove(argv[3]); return -1; }
             fclose(fout);
+            if (with_crc) {
+                const std::string ip = std::string(argv[3]) + ".idx";
+                if (FILE *fi = fopen(ip.c_str(), "wb")) {
+                    fprintf(fi, "NLZMIDX 2 1 %" PRIu64 " %" PRIu64 " %08X\n0 %" PRIu64 " %" PRIu64 " %08X\n", in_size, out_n, crc, out_n, in_size, crc);
+                    fclose(fi);
+                    printf("Block index: %s\n", ip.c_str());
+                }
+            }
             printf("Working... %" PRIu64 " -> %" PRIu64 "\n", in_size, out_n);
             printf("Done (input CRC32 %X, %.2f sec)\n", crc, (double)(w1.tv_sec - w0.tv_sec) + 1e-9 * (double)(w1.tv_nsec - w0.tv_nsec));
             nlzm_hip_shutdown();
@@ -186,6 +198,7 @@ int main(int argc, char **argv)
         clock_gettime(CLOCK_MONOTONIC, &w1);
         (void)t0;
         if (rc) { printf("Error: %s\n", nlzm_hip_last_error()); fclose(fout); remove(argv[3]); return -1; }
+        if (nstreams == 1) blen[0] = out_n;
         if (verify) {
             // the stream(s) decoded on the device, one workgroup each, and compared there with the input; neither comes back to the host
             uint64_t first = 0, decoded = 0;
@@ -205,20 +218,37 @@ int main(int argc, char **argv)
             (void)nlzm_hip_get_counter("decode_us", &dev_us);
             printf("Verified (%.2f sec, %.2f of them decoding on the device)\n", (double)(v1.tv_sec - v0.tv_sec) + 1e-9 * (double)(v1.tv_nsec - v0.tv_nsec), 1e-6 * (double)dev_us);
         }
+        // -crc: every block's CRC32 from the device, on a re-upload of the input as -verify makes one; the whole file's is their combination
+        std::vector<uint32_t> bcrc(nstreams, 0);
+        uint32_t whole = 0;
+        if (with_crc) {
+            std::vector<uint64_t> boff(nstreams), braw(nstreams);
+            const uint64_t per = (in.size() + nstreams - 1) / nstreams;
+            for (uint32_t i = 0; i < nstreams; i++) {
+                const uint64_t lo = (uint64_t)i * per < in.size() ? (uint64_t)i * per : in.size(), hi = lo + per < in.size() ? lo + per : in.size();
+                boff[i] = lo; braw[i] = hi - lo;
+            }
+            int crc_rc = ngpus ? nlzm_hip_init(0) : 0;
+            if (!crc_rc) crc_rc = nlzm_hip_crc32_ranges(in.data(), in.size(), nstreams, boff.data(), braw.data(), bcrc.data());
+            if (crc_rc) { printf("Error: crc: %s\n", nlzm_hip_last_error()); fclose(fout); remove(argv[3]); return -1; }
+            for (uint32_t i = 0; i < nstreams; i++) whole = nlzm_hip_crc32_combine(whole, bcrc[i], braw[i]);
+        }
         fwrite(out.data(), 1, (size_t)out_n, fout);
         fclose(fout);
-        if (nstreams > 1) {
+        if (nstreams > 1 || with_crc) {
             // the block index, a sidecar: where every block's stream starts, how long it is and how many input bytes it holds.  The
             // streams stay self-delimiting -- the index only saves d/t the hop over every frame header of every block before the parallel decode can
             // start, and keeps the later blocks' boundaries when the container is damaged inside an earlier one.
             const std::string ip = std::string(argv[3]) + ".idx";
             if (FILE *fi = fopen(ip.c_str(), "wb")) {
-                fprintf(fi, "NLZMIDX 1 %u %" PRIu64 " %" PRIu64 "\n", nstreams, (uint64_t)in.size(), out_n);
+                if (with_crc) fprintf(fi, "NLZMIDX 2 %u %" PRIu64 " %" PRIu64 " %08X\n", nstreams, (uint64_t)in.size(), out_n, whole);
+                else fprintf(fi, "NLZMIDX 1 %u %" PRIu64 " %" PRIu64 "\n", nstreams, (uint64_t)in.size(), out_n);
                 const uint64_t per = (in.size() + nstreams - 1) / nstreams;
                 uint64_t off = 0;
                 for (uint32_t i = 0; i < nstreams; i++) {
                     const uint64_t lo = (uint64_t)i * per < in.size() ? (uint64_t)i * per : in.size(), hi = lo + per < in.size() ? lo + per : in.size();
-                    fprintf(fi, "%" PRIu64 " %" PRIu64 " %" PRIu64 "\n", off, blen[i], hi - lo);
+                    if (with_crc) fprintf(fi, "%" PRIu64 " %" PRIu64 " %" PRIu64 " %08X\n", off, blen[i], hi - lo, bcrc[i]);
+                    else fprintf(fi, "%" PRIu64 " %" PRIu64 " %" PRIu64 "\n", off, blen[i], hi - lo);
                     off += blen[i];
                 }
                 fclose(fi);
@@ -226,7 +256,7 @@ int main(int argc, char **argv)
             }
         }
         printf("Working... %" PRIu64 " -> %" PRIu64 "\n", (uint64_t)in.size(), out_n);
-        printf("Done (input CRC32 %X, %.2f sec)\n", crc_calc(in.data(), in.size(), 0),
+        printf("Done (input CRC32 %X, %.2f sec)\n", with_crc ? whole : crc_calc(in.data(), in.size(), 0),
                (double)(w1.tv_sec - w0.tv_sec) + 1e-9 * (double)(w1.tv_nsec - w0.tv_nsec));
         nlzm_hip_shutdown();
     } else if ((argc == 4 && cmd == 'd') || (argc == 3 && cmd == 't')) {
@@ -246,10 +276,13 @@ int main(int argc, char **argv)
         // decoded on a host thread each, written in order
         std::vector<Span> parts;
         std::vector<uint64_t> raws;                 // (by index) the input bytes every block holds
+        std::vector<uint32_t> idx_crcs;             // (by a version-2 index) every block's CRC32, and the whole file's
+        uint32_t idx_whole = 0;
+        bool idx_has_crc = false;
         size_t cut_tail = 0;
         bool by_index = false;
         auto find_parts = [&](bool use_index) {
-            parts.clear(); raws.clear(); cut_tail = 0; by_index = false;
+            parts.clear(); raws.clear(); idx_crcs.clear(); cut_tail = 0; by_index = false; idx_has_crc = false;
             // the sidecar index of a block container, if it is there and fits the file: the blocks' boundaries without hopping over their frames
             const std::string ip = std::string(argv[2]) + ".idx";
             FILE *fi = use_index ? fopen(ip.c_str(), "rb") : nullptr;
@@ -258,20 +291,25 @@ int main(int argc, char **argv)
                 unsigned long long n_in = 0, n_out = 0;
                 std::vector<Span> idx;
                 std::vector<uint64_t> idx_raw;
-                bool ok = fscanf(fi, "NLZMIDX %u %u %llu %llu", &ver, &k, &n_in, &n_out) == 4 && ver == 1 && k >= 1 && k <= 4096 && n_out >= in.size();
+                std::vector<uint32_t> idx_crc;
+                unsigned whole = 0;
+                bool ok = fscanf(fi, "NLZMIDX %u %u %llu %llu", &ver, &k, &n_in, &n_out) == 4 && (ver == 1 || ver == 2) && k >= 1 && k <= 4096 && n_out >= in.size();
+                if (ok && ver == 2) ok = fscanf(fi, "%x", &whole) == 1;         // (version 2: version 1 and a CRC32 behind the header's and every block's fields)
                 unsigned long long expect = 0, raw_sum = 0;
                 bool cut = false;
                 for (unsigned i = 0; ok && i < k && !cut; i++) {
                     unsigned long long off = 0, len = 0, raw = 0;
-                    ok = fscanf(fi, "%llu %llu %llu", &off, &len, &raw) == 3 && off == expect && len >= 8 && off <= in.size() && raw <= n_in - raw_sum;
+                    unsigned bc = 0;
+                    ok = fscanf(fi, "%llu %llu %llu", &off, &len, &raw) == 3 && (ver == 1 || fscanf(fi, "%x", &bc) == 1) && off == expect && len >= 8 && off <= in.size() && raw <= n_in - raw_sum;
                     if (ok && len > in.size() - off) { cut = true; break; }      // (the file ends inside this block: the ones in front of it are whole; no off + len, which can wrap)
                     // (a block's stream starts with its header and ends with its terminator, :1915-1921, :646-648)
                     if (ok) ok = in[off] == 0 && in[off + 1] >= 10 && in[off + 1] <= 28 && be32(&in[off + len - 4]) == 0;
-                    if (ok) { idx.push_back(Span{ in.data() + off, (size_t)len }); idx_raw.push_back(raw); expect = off + len; raw_sum += raw; }
+                    if (ok) { idx.push_back(Span{ in.data() + off, (size_t)len }); idx_raw.push_back(raw); idx_crc.push_back(bc); expect = off + len; raw_sum += raw; }
                 }
                 fclose(fi);
                 if (ok && !idx.empty() && (cut || (expect == in.size() && n_out == in.size() && raw_sum == n_in))) {
                     parts = idx; raws = idx_raw; by_index = true;
+                    if (ver == 2) { idx_crcs = idx_crc; idx_whole = whole; idx_has_crc = true; }
                     if (cut) cut_tail = in.size() - (size_t)expect;
                 } else printf("Note: %s does not fit this file; the blocks are found by their frame headers\n", ip.c_str());
             }
@@ -295,12 +333,38 @@ int main(int argc, char **argv)
         };
         if (on_gpu && nlzm_hip_init(0)) { printf("Error: %s\n", nlzm_hip_last_error()); if (fout) { fclose(fout); remove(argv[3]); } return -1; }
         int rc = 0;
+        std::vector<uint32_t> got_crcs;             // what the blocks decoded to hash to (where a version-2 index gives CRCs to hold against)
+        uint64_t out_size = 0;
+        bool out_on_device = false;                 // t -gpu with a version-2 index: decoded and hashed on the device, nothing came back
         for (int attempt = 0; attempt < 2; attempt++) {
             find_parts(attempt == 0);
-            out.clear();
+            out.clear(); got_crcs.clear(); out_on_device = false; out_size = 0;
             rc = parts.empty() ? -3 : 0;
             bool index_wrong = false;               // a block did not decode to the bytes its index entry says it holds
-            if (!rc && on_gpu) {
+            if (!rc && on_gpu && idx_has_crc && cmd == 't') {
+                // nlzm_hip_check: decoded into a buffer on the device, every block bounded by its index entry, and hashed there
+                const uint32_t k = (uint32_t)parts.size();
+                std::vector<uint64_t> blen(k), raw(k);
+                for (uint32_t i = 0; i < k; i++) blen[i] = parts[i].n;
+                const uint64_t src_len = (uint64_t)(parts.back().p + parts.back().n - parts[0].p);
+                uint32_t first_bad = k;
+                got_crcs.assign(k, 0);
+                int drc = nlzm_hip_check(parts[0].p, src_len, k, blen.data(), raws.data(), idx_crcs.data(), &first_bad, got_crcs.data());
+                if (!drc && first_bad < k) {
+                    // a wrong length or a wrong CRC?  The blocks' own lengths say (a size pass; only a container that fails pays for it)
+                    uint64_t total = 0;
+                    drc = nlzm_hip_decompress_blocks(parts[0].p, src_len, k, blen.data(), nullptr, nullptr, 0, raw.data(), &total);
+                    for (uint32_t i = 0; !drc && i < k; i++) if (raw[i] != raws[i]) index_wrong = true;
+                }
+                if (drc == NLZM_HIP_E_NOMEM) { index_wrong = true; drc = 0; }
+                if (drc == NLZM_HIP_E_FORMAT) rc = -7;
+                else if (drc) { printf("Error: %s\n", nlzm_hip_last_error()); return -1; }
+                hb = parts[0].p[1]; fb = parts[0].p[3];
+                for (uint32_t i = 0; i < k; i++) out_size += raws[i];
+                out_on_device = true;
+                if (!index_wrong && !rc && k > 1) printf("Blocks: %d\n", (int)k);
+                if (index_wrong || rc) { out_size = 0; got_crcs.clear(); }
+            } else if (!rc && on_gpu) {
                 // all blocks at once on the device, one workgroup each; boundaries from above, raw lengths from the index where it gave them
                 std::vector<uint64_t> blen(parts.size()), raw(parts.size());
                 for (size_t i = 0; i < parts.size(); i++) blen[i] = parts[i].n;
@@ -337,8 +401,12 @@ int main(int argc, char **argv)
                 std::vector<int> rcs(parts.size(), 0);
                 std::vector<uint32_t> hbs(parts.size(), 0), fbs(parts.size(), 0);
                 std::vector<std::thread> th;
+                if (idx_has_crc) got_crcs.assign(parts.size(), 0);
                 for (size_t i = 0; i < parts.size(); i++)
-                    th.emplace_back([&, i] { rcs[i] = decode_stream(parts[i], outs[i], &hbs[i], &fbs[i]); });
+                    th.emplace_back([&, i] {
+                        rcs[i] = decode_stream(parts[i], outs[i], &hbs[i], &fbs[i]);
+                        if (!rcs[i] && idx_has_crc) got_crcs[i] = crc_calc(outs[i].data(), outs[i].size(), 0);
+                    });
                 for (auto &t : th) t.join();
                 for (size_t i = 0; i < parts.size() && !rc; i++) {
                     rc = rcs[i];
@@ -353,16 +421,45 @@ int main(int argc, char **argv)
             printf("Note: %s.idx does not describe this file's blocks; they are found by their frame headers\n", argv[2]);
         }
         if (rc) { printf("Assert failed: malformed stream (%d)\n", rc); if (fout) fclose(fout); return -1; }
+        const bool check_crc = by_index && idx_has_crc;
+        if (check_crc && got_crcs.empty()) {
+            // one stream, or d -gpu: the bytes are on the host, hashed there block by block
+            got_crcs.assign(parts.size(), 0);
+            std::vector<std::thread> th;
+            uint64_t at = 0;
+            for (size_t i = 0; i < parts.size(); i++) { th.emplace_back([&, i, at] { got_crcs[i] = crc_calc(out.data() + at, raws[i], 0); }); at += raws[i]; }
+            for (auto &t : th) t.join();
+        }
+        uint32_t out_crc = 0;
+        if (out_on_device) for (size_t i = 0; i < parts.size(); i++) out_crc = nlzm_hip_crc32_combine(out_crc, got_crcs[i], raws[i]);
+        else { out_crc = crc_calc(out.data(), out.size(), 0); out_size = out.size(); }
         printf("Dictionary: %d KB\n", (int)(((1ull << hb) + 1023) >> 10));
         printf("Frame: %d KB\n", (int)(((1u << fb) + 1023) >> 10));
         if (fout) { fwrite(out.data(), 1, out.size(), fout); fclose(fout); }
-        printf("Working... %" PRIu64 " -> %" PRIu64 "\n", (uint64_t)in.size(), (uint64_t)out.size());
-        printf("Done (output CRC32 %X, %.2f sec)\n", crc_calc(out.data(), out.size(), 0), (clock() - t0) / (double)CLOCKS_PER_SEC);
+        printf("Working... %" PRIu64 " -> %" PRIu64 "\n", (uint64_t)in.size(), out_size);
+        printf("Done (output CRC32 %X, %.2f sec)\n", out_crc, (clock() - t0) / (double)CLOCKS_PER_SEC);
+        bool crc_bad = false;
+        if (check_crc) {
+            // the index's CRCs against what decoded: every block, then -- where the container is whole -- their combination against the file's
+            uint32_t comb = 0;
+            for (size_t i = 0; i < parts.size(); i++) comb = nlzm_hip_crc32_combine(comb, got_crcs[i], raws[i]);
+            for (size_t i = 0; i < parts.size() && !crc_bad; i++)
+                if (got_crcs[i] != idx_crcs[i]) { printf("CRC32 MISMATCH in block %zu (index says %08X, decoded %08X)\n", i + 1, idx_crcs[i], got_crcs[i]); crc_bad = true; }
+            if (!crc_bad && !cut_tail && comb != idx_whole) { printf("CRC32 MISMATCH of the whole file (index says %08X, blocks combine to %08X)\n", idx_whole, comb); crc_bad = true; }
+            if (!crc_bad) printf("CRC32 ok (%zu blocks)\n", parts.size());
+            else if (fout) printf("Note: %s holds what decoded\n", argv[3]);
+        }
         if (cut_tail) { printf("Error: the container is cut off inside block %zu (%zu bytes of it present); %zu complete blocks decoded\n", parts.size() + 1, cut_tail, parts.size()); return -2; }
+        if (crc_bad) return -4;
     } else if (argc == 3 && cmd == 'h') {
         std::vector<uint8_t> in;
         if (!slurp(argv[2], in)) { printf("Error: %s file does not exist\n", argv[2]); return -1; }
-        printf("%X\n", crc_calc(in.data(), in.size(), 0));
+        uint32_t crc = 0;
+        if (on_gpu) {
+            if (nlzm_hip_init(0) || nlzm_hip_crc32(in.data(), in.size(), 0, &crc)) { printf("Error: %s\n", nlzm_hip_last_error()); return -1; }
+            nlzm_hip_shutdown();
+        } else crc = crc_calc(in.data(), in.size(), 0);
+        printf("%X\n", crc);
     } else {
         printf("Commands:\n"
                "\t[flags] c [input] [output] - Compress input file to output file (best parser)\n"
@@ -375,7 +472,9 @@ int main(int argc, char **argv)
                "\t-gpus:g = (this build) the blocks on GPUs 0..g-1 of this node, -blocks:k of them on each\n"
                "\t-verify = (this build) c decodes what it wrote on the GPU, one workgroup per stream, compares it with the input\n"
                "\t          and removes the output if they differ\n"
-               "\t-gpu = (this build) d / t decode on the GPU, all blocks of a container at once (without it they run on the host)\n");
+               "\t-gpu = (this build) d / t decode on the GPU, all blocks of a container at once (without it they run on the host); h hashes there\n"
+               "\t-crc = (this build) c hashes every block on the GPU and keeps the CRC32s in [output].idx (NLZMIDX 2), for one stream too;\n"
+               "\t       d / t compare what they decode with an index that holds CRC32s and exit with status -4 if a block differs\n");
     }
     return 0;
 }

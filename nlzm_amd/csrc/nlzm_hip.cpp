@@ -297,7 +297,7 @@ struct DevState {
     } rounds;
     // streaming host input (nlzm_hip_feed_*): two pinned staging buffers on a copy stream of their own
     struct Feed {
-        bool open = false;
+        bool open = false, finished = false;               // finished: feed_finish has succeeded (the input is whole in HBM)
         uint64_t n = 0, fed = 0, arrived = 0, taken = 0;    // input bytes handed over / known to be in HBM; output bytes handed back
         uint8_t *pin[2] = { nullptr, nullptr };
         hipEvent_t ev[2] = { nullptr, nullptr };
@@ -908,6 +908,9 @@ int host_stream(hipStream_t *st)
     return 0;
 }
 int decode_counter(const char *key, uint64_t *value);      // "decode_*": nlzm_hip_decode.cpp
+int crc_counter(const char *key, uint64_t *value);         // "crc_*": nlzm_hip_crc.cpp
+void crc_begin_call();
+int crc_ranges_on(hipStream_t st, const void *d_buf, uint64_t buf_len, uint32_t nranges, const uint64_t *off, const uint64_t *len, uint32_t seed, uint32_t *crc_out);
 }  // namespace nlzm
 
 extern "C" {
@@ -1070,6 +1073,7 @@ int nlzm_hip_get_counter(const char *key, uint64_t *value)
     Ctx &C = D.ctx;
     if (!key || !value) return set_err(NLZM_HIP_E_ARG, "null argument");
     if (!strncmp(key, "decode_", 7)) return nlzm::decode_counter(key, value);
+    if (!strncmp(key, "crc_", 4)) return nlzm::crc_counter(key, value);
     if (C.open) { const int rc = refresh_stats(C, D.opt.report != 0); if (rc) return rc; }
     static const struct { const char *name; int idx; } kProf[] = {
         { "finder_blocks", 0 }, { "table_blocks", 6 }, { "parser_blocks", 8 }, { "parser_passes", 13 },
@@ -1799,7 +1803,19 @@ int nlzm_hip_feed_finish(void)
     int rc = feed_run(D);
     if (!rc) { uint64_t total = 0; rc = stream_finish(D.ctx, &total, D.opt.report != 0); }
     if (rc) feed_close(D);
+    else F.finished = true;
     return rc;
+}
+// between feed_finish and feed_end: the CRC32 of the input that was fed, hashed where it lies (nlzm_hip_crc.cpp)
+int nlzm_hip_feed_input_crc32(uint32_t *crc)
+{
+    DevState &D = cur();
+    DevState::Feed &F = D.feed;
+    if (!F.open || !F.finished) return set_err(NLZM_HIP_E_ARG, "no finished feed (nlzm_hip_feed_input_crc32 goes between feed_finish and feed_end)");
+    if (!crc) return set_err(NLZM_HIP_E_ARG, "null argument");
+    nlzm::crc_begin_call();
+    const uint64_t off = 0, n = F.n;
+    return nlzm::crc_ranges_on(D.ctx.st, D.ctx.own_in, n, 1, &off, &n, 0, crc);
 }
 void nlzm_hip_feed_end(void) { feed_close(cur()); }
 

@@ -24,6 +24,9 @@ int host_stream(hipStream_t *st);
 void launch_decode(const void *d_args, void *d_res, uint32_t nstreams, hipStream_t st);
 void launch_split(const void *d_src, unsigned long long len, uint32_t nblocks, unsigned long long *d_block_len, uint32_t *d_bad, hipStream_t st);
 void launch_compare(const void *d_a, const void *d_b, unsigned long long n, unsigned long long *d_first, hipStream_t st);
+// nlzm_hip_crc.cpp
+void crc_begin_call();
+int crc_ranges_on(hipStream_t st, const void *d_buf, uint64_t buf_len, uint32_t nranges, const uint64_t *off, const uint64_t *len, uint32_t seed, uint32_t *crc_out);
 }  // namespace nlzm
 
 using namespace nlzm;
@@ -340,6 +343,65 @@ int nlzm_hip_verify(const uint8_t *src, uint64_t src_len, uint32_t nblocks, cons
     if (n) HIPCHK(hipMemcpyAsync(dorig.p, orig, n, hipMemcpyHostToDevice, st));
     HIPCHK(hipStreamSynchronize(st));
     return nlzm_hip_verify_dev(ds.p, src_len, nblocks, block_len, dorig.p, n, first_mismatch, decoded_len);
+}
+
+int nlzm_hip_check_dev(const void *d_src, uint64_t src_len, uint32_t nblocks, const uint64_t *block_len, const uint64_t *raw_len,
+                       const uint32_t *crc, uint32_t *first_bad, uint32_t *crc_out)
+{
+    hipStream_t st;
+    if (const int rc = host_stream(&st)) return rc;
+    if (!d_src || !crc || !first_bad || !nblocks || nblocks > 65536) return fail(NLZM_HIP_E_ARG, "null argument, or nblocks outside 1 .. 65536");
+    begin_call();
+    crc_begin_call();
+    // With the lengths the caller holds: ONE decode pass, every block bounded by its length.  A block that decodes to more or to less shows in
+    // that pass's error; the blocks are then sized and decoded by what they hold, as without lengths, and the comparison below names the block.
+    std::vector<uint64_t> raw(nblocks), off(nblocks);
+    DevBuf dd;
+    uint64_t total = 0;
+    int rc = NLZM_HIP_E_FORMAT;
+    if (raw_len) {
+        bool fits = true;
+        for (uint32_t i = 0; i < nblocks; i++) { if (raw_len[i] > ~0ull - total) fits = false; else total += raw_len[i]; }
+        if (fits && hipMalloc(&dd.p, total ? total : 16) == hipSuccess)
+            rc = blocks_dev(st, d_src, src_len, nblocks, block_len, raw_len, dd.p, total, raw.data(), &total);
+        else { (void)hipGetLastError(); dd.p = nullptr; }         // (lengths no buffer can hold are wrong lengths)
+        if (rc && rc != NLZM_HIP_E_CAPACITY && rc != NLZM_HIP_E_FORMAT) return rc;
+    }
+    if (rc) {
+        const double ms = g_last.ms;
+        rc = blocks_dev(st, d_src, src_len, nblocks, block_len, nullptr, nullptr, 0, raw.data(), &total);       // sizes
+        if (rc) return rc;
+        if (dd.p) { (void)hipFree(dd.p); dd.p = nullptr; }
+        rc = dd.alloc(total);
+        if (rc) return rc;
+        rc = blocks_dev(st, d_src, src_len, nblocks, block_len, raw.data(), dd.p, total, nullptr, &total);
+        g_last.ms += ms;
+        if (rc) return rc;
+    }
+    uint64_t at = 0;
+    for (uint32_t i = 0; i < nblocks; i++) { off[i] = at; at += raw[i]; }
+    std::vector<uint32_t> got(nblocks);
+    rc = crc_ranges_on(st, dd.p, total, nblocks, off.data(), raw.data(), 0, got.data());
+    if (rc) return rc;
+    uint32_t bad = nblocks;
+    for (uint32_t i = nblocks; i-- > 0;) if (got[i] != crc[i] || (raw_len && raw[i] != raw_len[i])) bad = i;
+    *first_bad = bad;
+    if (crc_out) memcpy(crc_out, got.data(), nblocks * sizeof(uint32_t));
+    return 0;
+}
+
+int nlzm_hip_check(const uint8_t *src, uint64_t src_len, uint32_t nblocks, const uint64_t *block_len, const uint64_t *raw_len,
+                   const uint32_t *crc, uint32_t *first_bad, uint32_t *crc_out)
+{
+    hipStream_t st;
+    if (const int rc = host_stream(&st)) return rc;
+    if (!src || !crc || !first_bad) return fail(NLZM_HIP_E_ARG, "null argument");
+    DevBuf ds;
+    const int rc = ds.alloc(src_len);
+    if (rc) return rc;
+    HIPCHK(hipMemcpyAsync(ds.p, src, src_len, hipMemcpyHostToDevice, st));
+    HIPCHK(hipStreamSynchronize(st));
+    return nlzm_hip_check_dev(ds.p, src_len, nblocks, block_len, raw_len, crc, first_bad, crc_out);
 }
 
 }  // extern "C"

@@ -1,0 +1,127 @@
+// crc_sim.cpp -- the CRC32 roles (nlzm_amd/csrc/nlzm_crc.h) run on the CPU, every lane a fiber (xw_sim.cpp).  TEST HARNESS ONLY
+// (tests/test_crc_sim.py, which holds the expected values: zlib's).
+//
+//   crc_sim <data> <cases>       one line of output per line of <cases>:
+//       C <start> <n> <align> <seed> <threads> <blocks>
+//           the n bytes of <data> from <start>, hashed from <seed> by <blocks> workgroups of <threads> lanes, twice: at <align> bytes behind
+//           a PROT_NONE page ("front"; alignment 0 starts right after it) and with the last byte flush against the PROT_NONE page behind
+//           ("back"; the start's alignment is then what the length leaves).  Prints both CRCs.
+//       R <bytes> <k> <off> <len> ... (k pairs)
+//           the first <bytes> bytes of <data> (a multiple of the page size: guard pages on both sides), k ranges in one call.  Prints k CRCs.
+//       G   prints the segment size.
+//
+// A read outside a range that leaves the mapping ends the harness with SIGSEGV: this is host code, which is where faults belong.
+#define NLZM_SIM 1
+#include "../../nlzm_amd/csrc/nlzm_crc.h"
+
+#include <stdio.h>
+#include <stdlib.h>
+#include <string.h>
+#include <sys/mman.h>
+#include <unistd.h>
+
+#include <vector>
+
+using namespace nlzm;
+
+namespace {
+
+struct Launch { crc::Args a; uint32_t threads; bool combine; };
+void entry(void *arg)
+{
+    const Launch *P = (const Launch *)arg;
+    if (P->combine) crc::combine_role(P->a, xw::block_index(), P->threads);
+    else crc::segments_role(P->a, P->threads, (unsigned long long)xw::block_index() * (P->threads / 64) + xw::wave(), (unsigned long long)xw::sim().nblocks * (P->threads / 64));
+}
+
+// the CRCs of k ranges of buf, as the library's host side sets a call up (nlzm_hip_crc.cpp: crc_ranges_on)
+std::vector<uint32_t> run(const uint8_t *buf, const std::vector<unsigned long long> &off, const std::vector<unsigned long long> &len, uint32_t seed, uint32_t threads,
+                          uint32_t blocks)
+{
+    const uint32_t k = (uint32_t)off.size();
+    std::vector<unsigned long long> o(off), l(len), seg0(k + 1);
+    o.push_back(0); l.push_back(0);
+    unsigned long long nsegs = 0;
+    for (uint32_t i = 0; i < k; i++) { seg0[i] = nsegs; nsegs += (len[i] + crc::kSegment - 1) / crc::kSegment; }
+    seg0[k] = nsegs;
+    std::vector<uint32_t> part(nsegs + 1, 0xDEADBEEFu), out(k, 0xDEADBEEFu);
+    Launch P{ crc::Args{ buf, o.data(), l.data(), seg0.data(), part.data(), out.data(), k, seed, nsegs }, threads, false };
+    if (nsegs) {
+        std::vector<unsigned long long> lds(blocks, sizeof(crc::Lds));
+        xw::launch(blocks, threads, lds.data(), entry, &P);
+    }
+    P.combine = true;
+    std::vector<unsigned long long> small(k, sizeof(crc::CombineLds));
+    xw::launch(k, threads, small.data(), entry, &P);
+    return out;
+}
+
+// `bytes` usable bytes between two PROT_NONE pages
+struct Guarded {
+    uint8_t *lo = nullptr, *hi = nullptr;           // first usable byte, the guard page behind
+    void make(size_t bytes)
+    {
+        const size_t pg = (size_t)sysconf(_SC_PAGESIZE), n = (bytes + pg - 1) / pg * pg;
+        uint8_t *m = (uint8_t *)mmap(nullptr, n + 2 * pg, PROT_READ | PROT_WRITE, MAP_PRIVATE | MAP_ANONYMOUS, -1, 0);
+        if (m == MAP_FAILED || mprotect(m, pg, PROT_NONE) || mprotect(m + pg + n, pg, PROT_NONE)) { fprintf(stderr, "crc_sim: no guarded buffer\n"); exit(2); }
+        lo = m + pg; hi = m + pg + n;
+    }
+};
+
+std::vector<uint8_t> slurp(const char *path)
+{
+    std::vector<uint8_t> b;
+    FILE *f = fopen(path, "rb");
+    if (!f) { fprintf(stderr, "cannot read %s\n", path); exit(2); }
+    fseek(f, 0, SEEK_END); const long sz = ftell(f); fseek(f, 0, SEEK_SET);
+    b.resize((size_t)sz);
+    if (sz && fread(b.data(), 1, (size_t)sz, f) != (size_t)sz) { fprintf(stderr, "short read\n"); exit(2); }
+    fclose(f);
+    return b;
+}
+
+}  // namespace
+
+int main(int argc, char **argv)
+{
+    if (argc != 3) { fprintf(stderr, "usage: see the head of crc_sim.cpp\n"); return 2; }
+    const std::vector<uint8_t> data = slurp(argv[1]);
+    FILE *f = fopen(argv[2], "r");
+    if (!f) { fprintf(stderr, "cannot read %s\n", argv[2]); return 2; }
+    Guarded g;
+    g.make(data.size() + 16);
+    const size_t room = (size_t)(g.hi - g.lo);
+    char kind[8];
+    while (fscanf(f, "%7s", kind) == 1) {
+        if (kind[0] == 'G') { printf("%llu\n", crc::kSegment); continue; }
+        if (kind[0] == 'C') {
+            unsigned long long start, n, align;
+            unsigned seed, threads, blocks;
+            if (fscanf(f, "%llu %llu %llu %u %u %u", &start, &n, &align, &seed, &threads, &blocks) != 6 || start + n > data.size() || align + n > room) return 2;
+            memset(g.lo, 0xA5, room);
+            uint8_t *front = g.lo + align;
+            if (n) memcpy(front, data.data() + start, n);
+            const uint32_t c0 = run(front, { 0 }, { n }, seed, threads, blocks)[0];
+            memset(g.lo, 0x5A, room);
+            uint8_t *back = g.hi - n;
+            if (n) memcpy(back, data.data() + start, n);
+            const uint32_t c1 = run(back, { 0 }, { n }, seed, threads, blocks)[0];
+            printf("%08X %08X\n", c0, c1);
+        } else if (kind[0] == 'R') {
+            unsigned long long bytes;
+            unsigned k;
+            if (fscanf(f, "%llu %u", &bytes, &k) != 2 || bytes > data.size() || bytes > room) return 2;
+            std::vector<unsigned long long> off(k), len(k);
+            for (unsigned i = 0; i < k; i++) if (fscanf(f, "%llu %llu", &off[i], &len[i]) != 2 || off[i] > bytes || len[i] > bytes - off[i]) return 2;
+            Guarded r;
+            r.make(bytes);
+            if ((size_t)(r.hi - r.lo) != bytes) return 2;
+            memcpy(r.lo, data.data(), bytes);
+            const std::vector<uint32_t> c = run(r.lo, off, len, 0, 128, 3);
+            for (unsigned i = 0; i < k; i++) printf("%08X%s", c[i], i + 1 < k ? " " : "\n");
+        } else return 2;
+    }
+    fclose(f);
+    printf("crc_sim: OK\n");
+    return 0;
+}
