@@ -285,6 +285,33 @@ int nlzm_hip_check_dev(const void *d_src, uint64_t src_len, uint32_t nblocks, co
 int nlzm_hip_check(const uint8_t *src, uint64_t src_len, uint32_t nblocks, const uint64_t *block_len, const uint64_t *raw_len,
                    const uint32_t *crc, uint32_t *first_bad, uint32_t *crc_out);
 
+/* ---- byte ranges out of a block container ---------------------------------------------------------------- */
+/* off[i], len[i] address the container's DECODED bytes: the blocks' contents back to back.  Ranges may be empty, overlap, repeat and come in any
+ * order; their bytes land in d_dst back to back in the caller's order, *dst_len is their sum (nranges == 0: success, *dst_len = 0).  A range with
+ * len > total - off is NLZM_HIP_E_ARG; *dst_len > dst_cap is NLZM_HIP_E_CAPACITY with nothing written.  nblocks: 1 .. 65536 (one stream: 1).
+ * block_len / raw_len as for nlzm_hip_decompress_blocks_dev: either may be NULL (the hop over the frame headers; a size pass of ALL blocks).
+ * With both given nothing but the needed blocks is touched: a block is needed when a non-empty range intersects it, is decoded ONCE per call, from
+ * its first byte (matches reach back) up to the furthest byte any range wants of it and no further (the decoder role's prefix mode, nlzm_decode.h),
+ * all needed blocks in one launch.  A block that exactly one range needs, from its first byte on, is decoded straight into d_dst; every other one
+ * into one scratch allocation of the library's (the sum of the prefixes needed; NLZM_HIP_E_NOMEM when there is no room -- no rounds), from where
+ * one gather launch moves all wanted parts out.  A block read in full that is longer / shorter than raw_len says: NLZM_HIP_E_CAPACITY /
+ * NLZM_HIP_E_FORMAT, as in nlzm_hip_decompress_blocks_dev; a block read in part that ends before the part does: NLZM_HIP_E_FORMAT.  A prefix
+ * read vouches for nothing behind the bytes it returns.
+ * crc (may be NULL; with it first_bad must not be): every block this call decoded IN FULL is hashed where it lies and compared; *first_bad is the
+ * first such block that differs, nblocks when none does; the return code is 0 either way, as nlzm_hip_check* has it.  Blocks read in part cannot
+ * be checked and are not: "range_blocks_checked" says how many were.
+ * Counters of the last call: "range_blocks_decoded", "range_blocks_direct", "range_blocks_checked", "range_decoded_bytes" (what the decoder
+ * produced: the cost), "range_returned_bytes", "range_scratch_bytes", "range_pieces" (what the gather launch moved), "range_us" (device time of
+ * the decode and the gather launch: "range_decode_us" + "range_gather_us"), "range_chunk_bytes" (needs no device); the "decode_*" counters
+ * describe the call's decode launch. */
+int nlzm_hip_read_ranges_dev(const void *d_src, uint64_t src_len, uint32_t nblocks, const uint64_t *block_len, const uint64_t *raw_len,
+                             const uint32_t *crc, uint32_t nranges, const uint64_t *off, const uint64_t *len,
+                             void *d_dst, uint64_t dst_cap, uint64_t *dst_len, uint32_t *first_bad);
+/* the same on host buffers: with block_len and raw_len given only the needed blocks' streams are uploaded, not the container */
+int nlzm_hip_read_ranges(const uint8_t *src, uint64_t src_len, uint32_t nblocks, const uint64_t *block_len, const uint64_t *raw_len,
+                         const uint32_t *crc, uint32_t nranges, const uint64_t *off, const uint64_t *len,
+                         uint8_t *dst, uint64_t dst_cap, uint64_t *dst_len, uint32_t *first_bad);
+
 /* ---- tuning knobs (defaults are what bench.py measures) -------------------- */
 /* key: "workers" (only 1: BT4 runs on per-head worker lanes), "batch_chunks" (chunks per persistent launch), "worker_blocks" (worker CUs of a stream, default 240: the stage CUs and these fill the device),
  * "worker_threads" (bin-taking lanes per worker CU, 64..512, default 128), "hot_waves" (waves per worker CU that take a hot

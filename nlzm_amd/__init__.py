@@ -34,6 +34,7 @@ ABI_SYMBOLS = [
     "nlzm_hip_decompress_dev", "nlzm_hip_decompress", "nlzm_hip_decompress_blocks_dev", "nlzm_hip_decompress_blocks", "nlzm_hip_verify_dev", "nlzm_hip_verify",
     "nlzm_hip_crc32_dev", "nlzm_hip_crc32", "nlzm_hip_crc32_ranges_dev", "nlzm_hip_crc32_ranges", "nlzm_hip_crc32_combine", "nlzm_hip_feed_input_crc32",
     "nlzm_hip_check_dev", "nlzm_hip_check",
+    "nlzm_hip_read_ranges_dev", "nlzm_hip_read_ranges",
 ]
 
 
@@ -131,6 +132,8 @@ def load_library() -> C.CDLL:
     lib.nlzm_hip_feed_input_crc32.argtypes = [u32p]
     lib.nlzm_hip_check_dev.argtypes = [C.c_void_p, C.c_uint64, C.c_uint32, u64p, u64p, u32p, u32p, u32p]
     lib.nlzm_hip_check.argtypes = [C.c_void_p, C.c_uint64, C.c_uint32, u64p, u64p, u32p, u32p, u32p]
+    lib.nlzm_hip_read_ranges_dev.argtypes = [C.c_void_p, C.c_uint64, C.c_uint32, u64p, u64p, u32p, C.c_uint32, u64p, u64p, C.c_void_p, C.c_uint64, u64p, u32p]
+    lib.nlzm_hip_read_ranges.argtypes = [C.c_void_p, C.c_uint64, C.c_uint32, u64p, u64p, u32p, C.c_uint32, u64p, u64p, C.c_void_p, C.c_uint64, u64p, u32p]
     _lib = lib
     return lib
 
@@ -332,6 +335,92 @@ def check(blob, crcs, nblocks: int = 1, raw_lens=None) -> int:
     bad = C.c_uint32(0)
     _chk(lib.nlzm_hip_check(src.ctypes.data, src.size, nblocks, None, raw, want, C.byref(bad), None))
     return int(bad.value)
+
+
+class CrcMismatch(NlzmError):
+    """read_ranges: a block that was decoded in full does not hash to the CRC32 the caller holds for it"""
+
+    def __init__(self, block: int):
+        super().__init__(f"block {block} (counted from 0) does not decode to bytes with the CRC32 given for it")
+        self.block = block
+
+
+def read_ranges(blob, ranges, nblocks: int = 1, block_lens=None, raw_lens=None, crcs=None) -> list[bytes]:
+    """The (offset, length) ranges of what `blob` (nblocks streams back to back) decodes to, all in one call on the device: only the blocks
+    some range needs are decoded, each once and only as far as the furthest byte wanted of it.  With block_lens and raw_lens (read_index
+    gives them) nothing else is touched or uploaded.  crcs: every block the call decoded in full is compared; CrcMismatch names the first
+    that differs (blocks read in part cannot be checked)."""
+    lib = load_library()
+    src = _bytes_in(blob)
+    k = len(ranges)
+    for name, v in (("block_lens", block_lens), ("raw_lens", raw_lens), ("crcs", crcs)):
+        if v is not None and len(v) != nblocks:
+            raise ValueError(f"{name}: one entry per block")
+    off, ln = (C.c_uint64 * max(1, k))(*[int(o) for o, _ in ranges]), (C.c_uint64 * max(1, k))(*[int(l) for _, l in ranges])
+    blen = (C.c_uint64 * nblocks)(*[int(x) for x in block_lens]) if block_lens is not None else None
+    raw = (C.c_uint64 * nblocks)(*[int(x) for x in raw_lens]) if raw_lens is not None else None
+    want = (C.c_uint32 * nblocks)(*[int(c) & 0xFFFFFFFF for c in crcs]) if crcs is not None else None
+    cap = sum(int(l) for _, l in ranges)
+    dst = np.empty(max(1, cap), dtype=np.uint8)
+    got, bad = C.c_uint64(0), C.c_uint32(nblocks)
+    _chk(lib.nlzm_hip_read_ranges(src.ctypes.data, src.size, nblocks, blen, raw, want, k, off, ln, dst.ctypes.data, cap, C.byref(got), C.byref(bad)))
+    if bad.value < nblocks:
+        raise CrcMismatch(int(bad.value))
+    out, pos = [], 0
+    for _, l in ranges:
+        out.append(dst[pos: pos + int(l)].tobytes())
+        pos += int(l)
+    assert pos == got.value
+    return out
+
+
+def read_range(blob, off: int, length: int, nblocks: int = 1, block_lens=None, raw_lens=None, crcs=None) -> bytes:
+    """read_ranges for one range"""
+    return read_ranges(blob, [(off, length)], nblocks, block_lens, raw_lens, crcs)[0]
+
+
+def read_index(path):
+    """The sidecar index of a block container (`nlzm c -blocks:k` writes NLZMIDX 1, with -crc NLZMIDX 2): (block_lens, raw_lens, crcs or None).
+    The structural checks are the command line's: offsets back to back, no sum that wraps 64 bits, block lengths summing to the header's
+    n_out and raw lengths to its n_in.  ValueError when the file is not such an index."""
+    words = open(path, "r").read().split()
+    M = 1 << 64
+
+    def num(w, base=10):
+        try:
+            v = int(w, base)
+        except ValueError:
+            raise ValueError(f"{path}: {w!r} is not a number") from None
+        if not 0 <= v < M:
+            raise ValueError(f"{path}: {w} does not fit 64 bits")
+        return v
+
+    if len(words) < 5 or words[0] != "NLZMIDX" or words[1] not in ("1", "2"):
+        raise ValueError(f"{path}: not an NLZMIDX 1 or 2 file")
+    ver, per = int(words[1]), 3 + (words[1] == "2")
+    k, n_in, n_out = num(words[2]), num(words[3]), num(words[4])
+    head = 5 + (ver == 2)
+    if not 1 <= k <= 65536 or len(words) != head + per * k:
+        raise ValueError(f"{path}: {k} blocks do not fit the file's {len(words)} fields")
+    if ver == 2 and num(words[5], 16) >= 1 << 32:
+        raise ValueError(f"{path}: the whole file's CRC32 does not fit 32 bits")
+    lens, raws, crcs, expect, raw_sum = [], [], [], 0, 0
+    for i in range(k):
+        f = words[head + per * i: head + per * (i + 1)]
+        off, ln, raw = num(f[0]), num(f[1]), num(f[2])
+        if off != expect or ln < 8 or off + ln >= M or ln > n_out - expect or raw > n_in - raw_sum:
+            raise ValueError(f"{path}: block {i + 1}'s entry does not fit (offset {off}, length {ln}, raw length {raw})")
+        if ver == 2:
+            c = num(f[3], 16)
+            if c >= 1 << 32:
+                raise ValueError(f"{path}: block {i + 1}'s CRC32 does not fit 32 bits")
+            crcs.append(c)
+        lens.append(ln)
+        raws.append(raw)
+        expect, raw_sum = expect + ln, raw_sum + raw
+    if expect != n_out or raw_sum != n_in:
+        raise ValueError(f"{path}: the blocks' lengths sum to {expect} / {raw_sum}, the header says {n_out} / {n_in}")
+    return lens, raws, (crcs if ver == 2 else None)
 
 
 def stats() -> dict:

@@ -2,7 +2,8 @@
 // (NLZM.cpp:2050-2178) in one file.  `c` runs the compress path on the GPU through
 // the C ABI of include/nlzm_hip.h and fails if no gfx950 device is present;
 // `d`/`t` decode on the host (the decoder is a serial byte-copy machine and stays
-// on the CPU: SURVEY.md 8f-1); `h` prints the CRC32.
+// on the CPU: SURVEY.md 8f-1); `h` prints the CRC32; `x` (not in the reference) writes byte ranges of what
+// a block container holds, reading only the blocks they need (host decoder, or nlzm_hip_read_ranges with -gpu).
 //
 // Messages, flag handling and exit codes follow the reference:
 //   flags lower-cased, leading '-' stripped, -window:N clamped to [15,28]   :2074-2092
@@ -63,6 +64,200 @@ using nlzm_host::decode_stream;
 
 void lower(char *v) { for (; *v; v++) *v = (char)(*v | 0x20); }
 
+// ---- x: byte ranges of what a container holds (not in the reference) -----------------------------------------------------------
+struct ByteRange { uint64_t off, len; };
+
+// The sidecar index as `x` needs it: the file itself is not consulted (it may be cut off behind the blocks a range needs), so the checks are
+// the structural ones -- no sum that wraps, offsets back to back, lengths summing to the header's n_out and raw lengths to its n_in.
+struct Index { std::vector<uint64_t> off, len, raw; std::vector<uint32_t> crc; bool has_crc = false; };
+bool read_index(const std::string &path, Index &ix)
+{
+    FILE *fi = fopen(path.c_str(), "rb");
+    if (!fi) return false;
+    unsigned ver = 0, k = 0, whole = 0;
+    unsigned long long n_in = 0, n_out = 0, expect = 0, raw_sum = 0;
+    bool ok = fscanf(fi, "NLZMIDX %u %u %llu %llu", &ver, &k, &n_in, &n_out) == 4 && (ver == 1 || ver == 2) && k >= 1 && k <= 65536;
+    if (ok && ver == 2) ok = fscanf(fi, "%x", &whole) == 1;
+    for (unsigned i = 0; ok && i < k; i++) {
+        unsigned long long off = 0, len = 0, raw = 0;
+        unsigned bc = 0;
+        ok = fscanf(fi, "%llu %llu %llu", &off, &len, &raw) == 3 && (ver == 1 || fscanf(fi, "%x", &bc) == 1) && off == expect && len >= 8 && len <= n_out - expect &&
+             raw <= n_in - raw_sum;
+        if (ok) { ix.off.push_back(off); ix.len.push_back(len); ix.raw.push_back(raw); ix.crc.push_back(bc); expect += len; raw_sum += raw; }
+    }
+    char extra[2];
+    if (ok && fscanf(fi, "%1s", extra) == 1) ok = false;       // (fields behind the last block's: not this index)
+    fclose(fi);
+    ix.has_crc = ver == 2;
+    return ok && expect == n_out && raw_sum == n_in;
+}
+
+int extract(const char *in_path, const char *out_path, const std::vector<ByteRange> &ranges, bool on_gpu)
+{
+    if (FILE *probe = fopen(out_path, "rb")) { printf("Error: %s already exists\n", out_path); fclose(probe); return -1; }
+    FILE *fin = fopen(in_path, "rb");
+    if (!fin) { printf("Error: %s file does not exist\n", in_path); return -1; }
+    fseeko(fin, 0, SEEK_END);
+    const uint64_t file_size = (uint64_t)ftello(fin);
+    Index ix;
+    std::vector<uint8_t> whole_file;                // (without an index: the container is read whole and split by its frame headers)
+    const bool by_index = read_index(std::string(in_path) + ".idx", ix);
+    const clock_t t0 = clock();
+    if (on_gpu && nlzm_hip_init(0)) { printf("Error: %s\n", nlzm_hip_last_error()); fclose(fin); return -1; }
+    std::vector<std::vector<uint8_t>> decoded;      // host path: the needed blocks, whole
+    if (!by_index) {
+        printf("Note: no usable %s.idx; the blocks are found by their frame headers and sized by decoding them\n", in_path);
+        ix = Index{};
+        whole_file.resize((size_t)file_size);
+        fseeko(fin, 0, SEEK_SET);
+        if (file_size && fread(whole_file.data(), 1, (size_t)file_size, fin) != (size_t)file_size) { printf("Error: %s could not be read\n", in_path); fclose(fin); return -1; }
+        for (size_t pos = 0; pos < whole_file.size();) {
+            const size_t l = stream_length(Span{ whole_file.data() + pos, whole_file.size() - pos });
+            if (!l) break;
+            ix.off.push_back(pos); ix.len.push_back(l); pos += l;
+        }
+        if (ix.off.empty()) { printf("Assert failed: malformed stream (-3)\n"); fclose(fin); return -1; }
+        ix.raw.assign(ix.off.size(), 0); ix.crc.assign(ix.off.size(), 0);
+        if (on_gpu) {
+            uint64_t total = 0;
+            if (nlzm_hip_decompress_blocks(whole_file.data(), ix.off.back() + ix.len.back(), (uint32_t)ix.off.size(), ix.len.data(), nullptr, nullptr, 0, ix.raw.data(), &total)) {
+                printf("Error: %s\n", nlzm_hip_last_error()); fclose(fin); return -1;
+            }
+        } else {
+            decoded.resize(ix.off.size());
+            std::vector<int> rcs(ix.off.size(), 0);
+            std::vector<std::thread> th;
+            for (size_t i = 0; i < ix.off.size(); i++)
+                th.emplace_back([&, i] { uint32_t hb, fb; rcs[i] = decode_stream(Span{ whole_file.data() + ix.off[i], (size_t)ix.len[i] }, decoded[i], &hb, &fb); });
+            for (auto &t : th) t.join();
+            for (size_t i = 0; i < ix.off.size(); i++) {
+                if (rcs[i]) { printf("Assert failed: malformed stream (%d)\n", rcs[i]); fclose(fin); return -1; }
+                ix.raw[i] = decoded[i].size();
+            }
+        }
+    }
+    const size_t k = ix.off.size();
+    std::vector<uint64_t> start(k + 1, 0);
+    for (size_t b = 0; b < k; b++) start[b + 1] = start[b] + ix.raw[b];         // (read_index: sums to n_in, does not wrap)
+    const uint64_t total = start[k];
+    uint64_t out_size = 0;
+    for (const ByteRange &r : ranges) {
+        if (r.off > total || r.len > total - r.off) {                             // (no off + len: it can wrap)
+            printf("Error: range %" PRIu64 ":%" PRIu64 " runs over the %" PRIu64 " bytes the container holds\n", r.off, r.len, total); fclose(fin); return -1;
+        }
+        out_size += r.len;
+    }
+    // the blocks some non-empty range intersects, and the furthest byte a range wants of each
+    std::vector<uint64_t> need(k, 0);
+    for (const ByteRange &r : ranges)
+        for (size_t b = 0; r.len && b < k; b++) {
+            if (!ix.raw[b] || start[b + 1] <= r.off || start[b] >= r.off + r.len) continue;
+            const uint64_t end = (r.off + r.len < start[b + 1] ? r.off + r.len : start[b + 1]) - start[b];
+            if (end > need[b]) need[b] = end;
+        }
+    // their streams: only those byte spans of the file, by seek and read
+    std::vector<size_t> picked;
+    std::vector<uint64_t> sub_off, sub_len, sub_raw, sub_start;
+    std::vector<uint32_t> sub_crc;
+    std::vector<uint8_t> packed;
+    uint64_t packed_len = 0, sub_total = 0;
+    for (size_t b = 0; b < k; b++) if (need[b]) {
+        picked.push_back(b); sub_off.push_back(packed_len); sub_len.push_back(ix.len[b]); sub_raw.push_back(ix.raw[b]); sub_crc.push_back(ix.crc[b]);
+        sub_start.push_back(sub_total);
+        packed_len += ix.len[b]; sub_total += ix.raw[b];
+    }
+    if (by_index || on_gpu) {
+        packed.resize((size_t)packed_len);
+        for (size_t i = 0; i < picked.size(); i++) {
+            const size_t b = picked[i];
+            bool ok = ix.off[b] <= file_size && ix.len[b] <= file_size - ix.off[b];
+            if (ok && whole_file.empty()) ok = !fseeko(fin, (off_t)ix.off[b], SEEK_SET) && fread(packed.data() + sub_off[i], 1, (size_t)ix.len[b], fin) == (size_t)ix.len[b];
+            else if (ok) memcpy(packed.data() + sub_off[i], whole_file.data() + ix.off[b], (size_t)ix.len[b]);
+            if (!ok) { printf("Error: the container is cut off inside block %zu, which a range needs\n", b + 1); fclose(fin); return -1; }
+        }
+    }
+    fclose(fin);
+    printf("Blocks: %zu, %zu of them read\n", k, picked.size());
+    // a range lies in consecutive blocks, all of them picked but the empty ones: in the picked blocks' contents it starts at
+    auto sub_of = [&](const ByteRange &r) {
+        if (!r.len) return (uint64_t)0;
+        size_t i = 0;
+        while (start[picked[i] + 1] <= r.off) i++;
+        return sub_start[i] + (r.off - start[picked[i]]);
+    };
+    std::vector<uint8_t> out((size_t)out_size);
+    size_t full = 0;
+    long bad_block = -1;
+    uint32_t bad_got = 0;
+    const bool check_crc = by_index && ix.has_crc;
+    for (size_t i = 0; i < picked.size(); i++) full += need[picked[i]] == ix.raw[picked[i]];
+    if (on_gpu) {
+        std::vector<uint64_t> off(ranges.size()), len(ranges.size());
+        for (size_t r = 0; r < ranges.size(); r++) { off[r] = sub_of(ranges[r]); len[r] = ranges[r].len; }
+        uint64_t got = 0;
+        uint32_t first_bad = (uint32_t)picked.size();
+        const int rc = picked.empty() ? 0
+                     : nlzm_hip_read_ranges(packed.data(), packed_len, (uint32_t)picked.size(), sub_len.data(), sub_raw.data(), check_crc ? sub_crc.data() : nullptr,
+                                            (uint32_t)ranges.size(), off.data(), len.data(), out.data(), out_size, &got, &first_bad);
+        if (rc == NLZM_HIP_E_FORMAT || rc == NLZM_HIP_E_CAPACITY) { printf("Error: a block does not decode to what its index entry says: %s\n", nlzm_hip_last_error()); return -1; }
+        if (rc) { printf("Error: %s\n", nlzm_hip_last_error()); return -1; }
+        if (check_crc && first_bad < picked.size()) {
+            // (what the block hashes to, for the message: decoded once more on the host, on this path only)
+            std::vector<uint8_t> o; uint32_t hb, fb;
+            (void)decode_stream(Span{ packed.data() + sub_off[first_bad], (size_t)sub_len[first_bad] }, o, &hb, &fb);
+            bad_block = (long)picked[first_bad]; bad_got = crc_calc(o.data(), o.size(), 0);
+        }
+        nlzm_hip_shutdown();
+    } else {
+        // the needed blocks decoded whole by the host decoder, one thread per block, and sliced
+        if (decoded.empty()) {
+            decoded.resize(k);
+            std::vector<int> rcs(picked.size(), 0);
+            std::vector<std::thread> th;
+            for (size_t i = 0; i < picked.size(); i++)
+                th.emplace_back([&, i] { uint32_t hb, fb; rcs[i] = decode_stream(Span{ packed.data() + sub_off[i], (size_t)sub_len[i] }, decoded[picked[i]], &hb, &fb); });
+            for (auto &t : th) t.join();
+            for (size_t i = 0; i < picked.size(); i++) {
+                if (rcs[i]) { printf("Assert failed: malformed stream (%d)\n", rcs[i]); return -1; }
+                if (decoded[picked[i]].size() != ix.raw[picked[i]]) {
+                    printf("Error: block %zu decodes to %zu bytes, its index entry says %" PRIu64 "\n", picked[i] + 1, decoded[picked[i]].size(), ix.raw[picked[i]]);
+                    return -1;
+                }
+            }
+        }
+        uint64_t at = 0;
+        for (const ByteRange &r : ranges) {
+            for (size_t b = 0; r.len && b < k; b++) {
+                if (!ix.raw[b] || start[b + 1] <= r.off || start[b] >= r.off + r.len) continue;
+                const uint64_t from = r.off > start[b] ? r.off : start[b], to = r.off + r.len < start[b + 1] ? r.off + r.len : start[b + 1];
+                memcpy(out.data() + at + (from - r.off), decoded[b].data() + (from - start[b]), (size_t)(to - from));
+            }
+            at += r.len;
+        }
+        for (size_t i = 0; check_crc && i < picked.size() && bad_block < 0; i++) {
+            const size_t b = picked[i];
+            if (need[b] != ix.raw[b]) continue;
+            const uint32_t c = crc_calc(decoded[b].data(), decoded[b].size(), 0);
+            if (c != ix.crc[b]) { bad_block = (long)b; bad_got = c; }
+        }
+    }
+    FILE *fout = fopen(out_path, "wb");
+    if (!fout) { printf("Error: %s file does not exist\n", out_path); return -1; }
+    fwrite(out.data(), 1, out.size(), fout);
+    fclose(fout);
+    printf("Working... %zu ranges -> %" PRIu64 "\n", ranges.size(), out_size);
+    printf("Done (output CRC32 %X, %.2f sec)\n", crc_calc(out.data(), out.size(), 0), (clock() - t0) / (double)CLOCKS_PER_SEC);
+    if (check_crc) {
+        if (bad_block >= 0) {
+            printf("CRC32 MISMATCH in block %ld (index says %08X, decoded %08X)\n", bad_block + 1, ix.crc[(size_t)bad_block], bad_got);
+            printf("Note: %s holds what decoded\n", out_path);
+            return -4;
+        }
+        printf("CRC32 ok (%zu of %zu blocks read in full)\n", full, picked.size());
+    }
+    return 0;
+}
+
 }  // namespace
 
 int main(int argc, char **argv)
@@ -78,6 +273,7 @@ int main(int argc, char **argv)
     bool verify = false;                            // -verify (not in the reference): c decodes what it wrote on the device and compares it with the input
     bool with_crc = false;                          // -crc (not in the reference): c keeps every block's CRC32, hashed on the device, in the index (NLZMIDX 2); d / t check them
     bool on_gpu = false;                            // -gpu (not in the reference): d / t decode on the device; without it they are host-only and need none
+    std::vector<ByteRange> ranges;                  // -range:off:len (not in the reference): what x writes, in this order
     while (argc >= 2 && *argv[1] == '-') {
         char *arg = argv[1];
         argv++; argc--;
@@ -101,6 +297,20 @@ int main(int argc, char **argv)
             with_crc = true;
         } else if (!strcmp(arg, "gpu")) {
             on_gpu = true;
+        } else if (!strncmp(arg, "range:", 6)) {
+            // digits ':' digits and nothing else; a number that does not fit 64 bits is refused, not saturated
+            auto number = [](const char *&p, unsigned long long &v) {
+                if (*p < '0' || *p > '9') return false;
+                for (v = 0; *p >= '0' && *p <= '9'; p++) {
+                    if (v > (~0ull - (unsigned long long)(*p - '0')) / 10) return false;
+                    v = v * 10 + (unsigned long long)(*p - '0');
+                }
+                return true;
+            };
+            const char *p = arg + 6;
+            unsigned long long off = 0, len = 0;
+            if (!number(p, off) || *p++ != ':' || !number(p, len) || *p) { printf("Unrecognized flag %s\n", arg); return -1; }
+            ranges.push_back(ByteRange{ off, len });
         } else {
             printf("Unrecognized flag %s\n", arg);
             return -1;
@@ -451,6 +661,8 @@ int main(int argc, char **argv)
         }
         if (cut_tail) { printf("Error: the container is cut off inside block %zu (%zu bytes of it present); %zu complete blocks decoded\n", parts.size() + 1, cut_tail, parts.size()); return -2; }
         if (crc_bad) return -4;
+    } else if (argc == 4 && cmd == 'x' && !ranges.empty()) {
+        return extract(argv[2], argv[3], ranges, on_gpu);
     } else if (argc == 3 && cmd == 'h') {
         std::vector<uint8_t> in;
         if (!slurp(argv[2], in)) { printf("Error: %s file does not exist\n", argv[2]); return -1; }
@@ -466,6 +678,7 @@ int main(int argc, char **argv)
                "\td [input] [output] - Decompress input file to output file\n"
                "\tt [input] - Decompress input file in memory\n"
                "\th [input] - Calculate CRC32 for input file\n"
+               "\t-range:off:len [-range:...] x [input] [output] - (this build) write those byte ranges of what a block container holds; needs [input].idx\n"
                "Flags:\n"
                "\t-window:bits = Maximum window size in bits, default 22 (4 MB), min 15, max 28 (32 KB to 256 MB)\n"
                "\t-blocks:k = (this build) compress k independent blocks at once; d/t read the streams back to back\n"

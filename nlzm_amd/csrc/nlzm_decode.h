@@ -47,7 +47,16 @@ struct StreamArgs {
     const uint8_t *src; unsigned long long len;     // reads stay inside [src, src + len)
     uint8_t *dst; unsigned long long cap;           // writes stay inside [dst, dst + cap); dst == nullptr: size only, nothing is stored
     unsigned long long budget;                      // clock100() ticks the decode may take
+    uint32_t flags = 0;                             // kPrefix
 };
+// kPrefix: reaching `cap` ends the decode SUCCESSFULLY (rc = kOk, out_len = cap): the literal that would land at dst + cap is not
+// written (not even decoded: the decode stops behind the op that brings n to cap), a match that runs over it is copied up to it
+// exactly, the ring is flushed in full.  What the stream holds behind the op that reaches `cap` is not looked at -- no later op, no
+// frame end, no frame header, no terminator; cap = 0 reads the stream's four header bytes and nothing else: a prefix read vouches for
+// NOTHING behind the bytes it returns (a stream damaged there decodes as if it were whole).  The counters (syms, n_literal, ...)
+// count the ops up to and including the one that reached `cap`.  A stream that ends before `cap` reports its true, shorter out_len.
+// Without the flag a `cap` below the stream's length stays kErrCapacity.
+enum : uint32_t { kPrefix = 1u };
 struct StreamResult {
     int rc; uint32_t detail;                        // detail: the host decoder's code for a format error (-1 .. -7, negated)
     unsigned long long out_len;                     // bytes decoded (an error: up to where it was noticed)
@@ -237,11 +246,10 @@ XW_FN void flush(Out &O, bool all)
     xw::drain();
     xw::wave_sync();
 }
-// lv bytes from dv back (dv <= n checked by the caller).  false: dst_cap is too small, nothing of the match written
-XW_FN bool copy(Out &O, uint32_t dv, uint32_t lv)
+// lv bytes from dv back (dv <= n and n + lv <= cap checked by the caller)
+XW_FN void copy(Out &O, uint32_t dv, uint32_t lv)
 {
-    if (!O.store) { O.n += lv; return true; }
-    if (O.n + lv > O.cap) return false;
+    if (!O.store) { O.n += lv; return; }
     uint8_t *ring = xw::lds<Lds>()->ring;
     const unsigned long long from = O.n - dv;
     const bool periodic = dv < lv;                  // the source runs into the match itself: byte i is byte i % dv (the host's byte loop defines it)
@@ -273,7 +281,6 @@ XW_FN bool copy(Out &O, uint32_t dv, uint32_t lv)
         xw::wave_sync();
     }
     O.n += lv;
-    return true;
 }
 
 // ---- the role ----------------------------------------------------------------------------------------------------------------------
@@ -294,6 +301,7 @@ XW_FN void decode_role(const StreamArgs &A, StreamResult *res)
     Count C{ 0, 0, 0 };
     unsigned long long n_literal = 0, n_dict = 0, n_rep = 0, copy_cycles = 0;
     const unsigned long long len = A.len;
+    const bool prefix = (A.flags & kPrefix) && O.store;
     int rc = kOk;
     uint32_t detail = 0;
 #define DEC_FAIL(code, why) { rc = (code); detail = (why); break; }
@@ -306,6 +314,7 @@ XW_FN void decode_role(const StreamArgs &A, StreamResult *res)
         unsigned long long pos = 4;
         uint32_t ops_seen = 0;
         for (;;) {
+            if (prefix && O.n >= O.cap) break;              // the prefix is whole: not a byte of what follows is looked at, no frame header either
             if (pos + 4 > len) DEC_FAIL(kErrFormat, 3)
             Frame F;
             F.num_ops = ld_be32(S, pos);
@@ -336,7 +345,7 @@ XW_FN void decode_role(const StreamArgs &A, StreamResult *res)
                     vadd(n_literal, 1);
                     if (O.store) {
                         if (F.bad) break;                           // (the host decoder's byte is garbage then, and the stream rejected)
-                        if (O.n >= O.cap) DEC_FAIL(kErrCapacity, 0)
+                        if (O.n >= O.cap) DEC_FAIL(kErrCapacity, 0)        // (prefix mode never gets here with n == cap: it has stopped)
                         if (xw::lane() == 0) xw::lds<Lds>()->ring[(O.n + O.a) & (kRing - 1)] = (uint8_t)((hi << 4) + lo);
                     }
                     O.n++;
@@ -370,7 +379,14 @@ XW_FN void decode_role(const StreamArgs &A, StreamResult *res)
                     if (F.bad) break;                               // (what was decoded after the frame ran out is garbage; the stream is rejected below)
                     if (dv > O.n) DEC_FAIL(kErrFormat, 6)
                     const unsigned long long t0 = xw::tick();
-                    if (!copy(O, dv, lv)) DEC_FAIL(kErrCapacity, 0)
+                    if (O.store && O.n + lv > O.cap) {
+                        if (!prefix) DEC_FAIL(kErrCapacity, 0)                     // (nothing of the match written)
+                        // the cut match: its first cap - n bytes, by the same copy -- bytes i < lv' of a periodic match are those of the whole one
+                        copy(O, dv, (uint32_t)(O.cap - O.n));
+                        vadd(copy_cycles, xw::tick() - t0);
+                        break;
+                    }
+                    copy(O, dv, lv);
                     vadd(copy_cycles, xw::tick() - t0);
                 }
                 if (O.store && O.n - O.fl >= kFlush) {
@@ -378,6 +394,7 @@ XW_FN void decode_role(const StreamArgs &A, StreamResult *res)
                     flush(O, false);
                     vadd(copy_cycles, xw::tick() - t0);
                 }
+                if (prefix && O.n >= O.cap) break;          // ... and no further op (the frame loop's test ends the decode)
             }
             if (rc) break;
             if (F.bad) DEC_FAIL(kErrFormat, 7)

@@ -909,6 +909,7 @@ int host_stream(hipStream_t *st)
 }
 int decode_counter(const char *key, uint64_t *value);      // "decode_*": nlzm_hip_decode.cpp
 int crc_counter(const char *key, uint64_t *value);         // "crc_*": nlzm_hip_crc.cpp
+int range_counter(const char *key, uint64_t *value);       // "range_*": nlzm_hip_range.cpp
 void crc_begin_call();
 int crc_ranges_on(hipStream_t st, const void *d_buf, uint64_t buf_len, uint32_t nranges, const uint64_t *off, const uint64_t *len, uint32_t seed, uint32_t *crc_out);
 }  // namespace nlzm
@@ -1074,6 +1075,7 @@ int nlzm_hip_get_counter(const char *key, uint64_t *value)
     if (!key || !value) return set_err(NLZM_HIP_E_ARG, "null argument");
     if (!strncmp(key, "decode_", 7)) return nlzm::decode_counter(key, value);
     if (!strncmp(key, "crc_", 4)) return nlzm::crc_counter(key, value);
+    if (!strncmp(key, "range_", 6)) return nlzm::range_counter(key, value);
     if (C.open) { const int rc = refresh_stats(C, D.opt.report != 0); if (rc) return rc; }
     static const struct { const char *name; int idx; } kProf[] = {
         { "finder_blocks", 0 }, { "table_blocks", 6 }, { "parser_blocks", 8 }, { "parser_passes", 13 },

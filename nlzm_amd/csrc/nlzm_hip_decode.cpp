@@ -84,14 +84,10 @@ struct Events {
 // so this is an order of magnitude above any well-formed stream and still ends a decode that has gone wrong.
 unsigned long long budget_for(uint64_t stream_len) { return (60ull + stream_len / 1000000ull) * 100000000ull; }
 
-// one launch: stream i = [d_src + off[i], + len[i]) -> d_dst + dst_off[i], at most cap[i] bytes (d_dst == nullptr: sizes only)
-int run_pass(hipStream_t st, const uint8_t *d_src, const std::vector<uint64_t> &off, const std::vector<uint64_t> &len, uint8_t *d_dst,
-             const std::vector<uint64_t> &dst_off, const std::vector<uint64_t> &cap, std::vector<dec::StreamResult> &res)
+// one launch of the streams in `args` (a destination pointer, a bound and the flags per stream); res: what each reported
+int run_streams(hipStream_t st, const std::vector<dec::StreamArgs> &args, std::vector<dec::StreamResult> &res)
 {
-    const size_t k = off.size();
-    std::vector<dec::StreamArgs> args(k);
-    for (size_t i = 0; i < k; i++)
-        args[i] = dec::StreamArgs{ d_src + off[i], len[i], d_dst ? d_dst + dst_off[i] : nullptr, d_dst ? cap[i] : ~0ull, budget_for(len[i]) };
+    const size_t k = args.size();
     DevBuf da, dr;
     int rc = da.alloc(k * sizeof(dec::StreamArgs));
     if (!rc) rc = dr.alloc(k * sizeof(dec::StreamResult));
@@ -129,10 +125,21 @@ int run_pass(hipStream_t st, const uint8_t *d_src, const std::vector<uint64_t> &
         if (r.rc == dec::kErrFormat)
             return fail(NLZM_HIP_E_FORMAT, "stream %zu of %zu is not a well-formed NLZM stream (check %u failed after %llu output bytes)", i + 1, k, r.detail, r.out_len);
         if (r.rc == dec::kErrCapacity)
-            return fail(NLZM_HIP_E_CAPACITY, "stream %zu of %zu decodes to more than the %llu bytes there is room for", i + 1, k, (unsigned long long)cap[i]);
+            return fail(NLZM_HIP_E_CAPACITY, "stream %zu of %zu decodes to more than the %llu bytes there is room for", i + 1, k, (unsigned long long)args[i].cap);
         if (r.rc) return fail(NLZM_HIP_E_KERNEL, "decode kernel: stream %zu of %zu ended with code %d after %llu output bytes", i + 1, k, r.rc, r.out_len);
     }
     return 0;
+}
+
+// stream i = [d_src + off[i], + len[i]) -> d_dst + dst_off[i], at most cap[i] bytes (d_dst == nullptr: sizes only)
+int run_pass(hipStream_t st, const uint8_t *d_src, const std::vector<uint64_t> &off, const std::vector<uint64_t> &len, uint8_t *d_dst,
+             const std::vector<uint64_t> &dst_off, const std::vector<uint64_t> &cap, std::vector<dec::StreamResult> &res)
+{
+    const size_t k = off.size();
+    std::vector<dec::StreamArgs> args(k);
+    for (size_t i = 0; i < k; i++)
+        args[i] = dec::StreamArgs{ d_src + off[i], len[i], d_dst ? d_dst + dst_off[i] : nullptr, d_dst ? cap[i] : ~0ull, budget_for(len[i]) };
+    return run_streams(st, args, res);
 }
 
 void begin_call() { g_last.ms = 0; g_last.passes = 0; }
@@ -196,6 +203,15 @@ int blocks_dev(hipStream_t st, const void *d_src, uint64_t src_len, uint32_t nbl
 }  // namespace
 
 namespace nlzm {
+// what the range reader (nlzm_hip_range.cpp) shares with the entries here
+void decode_begin_call() { begin_call(); }
+double decode_call_ms() { return g_last.ms; }
+unsigned long long decode_budget_for(uint64_t stream_len) { return budget_for(stream_len); }
+int decode_run_streams(hipStream_t st, const std::vector<dec::StreamArgs> &args, std::vector<dec::StreamResult> &res) { return run_streams(st, args, res); }
+int decode_split(hipStream_t st, const void *d_src, uint64_t src_len, uint32_t nblocks, const uint64_t *block_len, std::vector<uint64_t> &off, std::vector<uint64_t> &len)
+{
+    return split(st, d_src, src_len, nblocks, block_len, off, len);
+}
 int decode_counter(const char *key, uint64_t *value)
 {
     static const struct { const char *name; unsigned long long dec::StreamResult::*m; } kSum[] = {

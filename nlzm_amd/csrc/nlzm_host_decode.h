@@ -118,7 +118,7 @@ inline size_t stream_length(const Span &in)
 }
 
 // (distance, length) of every match, for tests that must know what a stream contains
-struct MatchLog { std::vector<uint32_t> dv, lv; };
+struct MatchLog { std::vector<uint32_t> dv, lv; std::vector<uint64_t> at; };      // at: the output offset a match starts at
 
 // returns 0 or a negative code; out receives the decoded bytes
 inline int decode_stream(const Span &in, std::vector<uint8_t> &out, uint32_t *hist_bits, uint32_t *frame_bits, Counts *cnt = nullptr,
@@ -178,7 +178,7 @@ inline int decode_stream(const Span &in, std::vector<uint8_t> &out, uint32_t *hi
             lv += match_min(dv);
             rep_add(m->rep, dv);
             if (dv > out.size()) { rc = -6; break; }
-            if (log) { log->dv.push_back(dv); log->lv.push_back(lv); }
+            if (log) { log->dv.push_back(dv); log->lv.push_back(lv); log->at.push_back(out.size()); }
             const size_t from = out.size() - dv;
             for (uint32_t i = 0; i < lv; i++) out.push_back(out[from + i]);
         }
