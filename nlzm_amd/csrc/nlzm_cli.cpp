@@ -23,6 +23,7 @@
 
 #include "../../include/nlzm_hip.h"
 #include "nlzm_host_decode.h"
+#include "nlzm_read_plan.h"
 
 namespace {
 
@@ -111,12 +112,9 @@ int extract(const char *in_path, const char *out_path, const std::vector<ByteRan
         whole_file.resize((size_t)file_size);
         fseeko(fin, 0, SEEK_SET);
         if (file_size && fread(whole_file.data(), 1, (size_t)file_size, fin) != (size_t)file_size) { printf("Error: %s could not be read\n", in_path); fclose(fin); return -1; }
-        for (size_t pos = 0; pos < whole_file.size();) {
-            const size_t l = stream_length(Span{ whole_file.data() + pos, whole_file.size() - pos });
-            if (!l) break;
-            ix.off.push_back(pos); ix.len.push_back(l); pos += l;
-        }
-        if (ix.off.empty()) { printf("Assert failed: malformed stream (-3)\n"); fclose(fin); return -1; }
+        if (!nlzm_host::split_streams(Span{ whole_file.data(), whole_file.size() }, SIZE_MAX, ix.len)) { printf("Assert failed: malformed stream (-3)\n"); fclose(fin); return -1; }
+        ix.off.assign(ix.len.size(), 0);
+        for (size_t i = 1; i < ix.len.size(); i++) ix.off[i] = ix.off[i - 1] + ix.len[i - 1];
         ix.raw.assign(ix.off.size(), 0); ix.crc.assign(ix.off.size(), 0);
         if (on_gpu) {
             uint64_t total = 0;
@@ -137,24 +135,18 @@ int extract(const char *in_path, const char *out_path, const std::vector<ByteRan
         }
     }
     const size_t k = ix.off.size();
-    std::vector<uint64_t> start(k + 1, 0);
-    for (size_t b = 0; b < k; b++) start[b + 1] = start[b] + ix.raw[b];         // (read_index: sums to n_in, does not wrap)
-    const uint64_t total = start[k];
-    uint64_t out_size = 0;
-    for (const ByteRange &r : ranges) {
-        if (r.off > total || r.len > total - r.off) {                             // (no off + len: it can wrap)
-            printf("Error: range %" PRIu64 ":%" PRIu64 " runs over the %" PRIu64 " bytes the container holds\n", r.off, r.len, total); fclose(fin); return -1;
-        }
-        out_size += r.len;
+    // the library's plan (nlzm_read_plan.h): the ranges checked against what the container holds; need[b], the furthest byte a range wants of block b
+    std::vector<uint64_t> off(ranges.size()), len(ranges.size());
+    for (size_t r = 0; r < ranges.size(); r++) { off[r] = ranges[r].off; len[r] = ranges[r].len; }
+    nlzm::range::Plan plan;
+    char why[512];
+    if (nlzm::range::make_plan(plan, (uint32_t)k, ix.raw.data(), (uint32_t)ranges.size(), off.data(), len.data(), ~0ull, nlzm::ErrText{ why, sizeof why })) {
+        if (plan.bad_range < ranges.size()) printf("Error: range %" PRIu64 ":%" PRIu64 " runs over the %" PRIu64 " bytes the container holds\n", off[plan.bad_range], len[plan.bad_range], plan.total);
+        else printf("Error: %s\n", why);
+        fclose(fin); return -1;
     }
-    // the blocks some non-empty range intersects, and the furthest byte a range wants of each
-    std::vector<uint64_t> need(k, 0);
-    for (const ByteRange &r : ranges)
-        for (size_t b = 0; r.len && b < k; b++) {
-            if (!ix.raw[b] || start[b + 1] <= r.off || start[b] >= r.off + r.len) continue;
-            const uint64_t end = (r.off + r.len < start[b + 1] ? r.off + r.len : start[b + 1]) - start[b];
-            if (end > need[b]) need[b] = end;
-        }
+    const std::vector<uint64_t> &start = plan.start, &need = plan.need;
+    const uint64_t out_size = plan.dst_len;
     // their streams: only those byte spans of the file, by seek and read
     std::vector<size_t> picked;
     std::vector<uint64_t> sub_off, sub_len, sub_raw, sub_start;
@@ -192,8 +184,7 @@ int extract(const char *in_path, const char *out_path, const std::vector<ByteRan
     const bool check_crc = by_index && ix.has_crc;
     for (size_t i = 0; i < picked.size(); i++) full += need[picked[i]] == ix.raw[picked[i]];
     if (on_gpu) {
-        std::vector<uint64_t> off(ranges.size()), len(ranges.size());
-        for (size_t r = 0; r < ranges.size(); r++) { off[r] = sub_of(ranges[r]); len[r] = ranges[r].len; }
+        for (size_t r = 0; r < ranges.size(); r++) off[r] = sub_of(ranges[r]);
         uint64_t got = 0;
         uint32_t first_bad = (uint32_t)picked.size();
         const int rc = picked.empty() ? 0
@@ -227,11 +218,9 @@ int extract(const char *in_path, const char *out_path, const std::vector<ByteRan
         }
         uint64_t at = 0;
         for (const ByteRange &r : ranges) {
-            for (size_t b = 0; r.len && b < k; b++) {
-                if (!ix.raw[b] || start[b + 1] <= r.off || start[b] >= r.off + r.len) continue;
-                const uint64_t from = r.off > start[b] ? r.off : start[b], to = r.off + r.len < start[b + 1] ? r.off + r.len : start[b + 1];
+            nlzm::range::for_each_part(start, (uint32_t)k, r.off, r.len, [&](uint32_t b, uint64_t from, uint64_t to) {
                 memcpy(out.data() + at + (from - r.off), decoded[b].data() + (from - start[b]), (size_t)(to - from));
-            }
+            });
             at += r.len;
         }
         for (size_t i = 0; check_crc && i < picked.size() && bad_block < 0; i++) {

@@ -897,7 +897,9 @@ int stream_finish(Ctx &C, uint64_t *dst_len, bool report)
 
 }  // namespace
 
-// ---- what the decoder's entry points (nlzm_hip_decode.cpp) use of this file's state: the error text, the library's stream ----
+// ---- what the read side's entry points (nlzm_hip_decode.cpp, nlzm_hip_crc.cpp, nlzm_hip_range.cpp) use of this file's state: the error
+// text, the library's stream; what this file uses of theirs is declared in the same header ----
+#include "nlzm_host_util.h"
 namespace nlzm {
 int host_error(int code, const char *text) { return set_err(code, "%s", text); }
 int host_stream(hipStream_t *st)
@@ -907,11 +909,6 @@ int host_stream(hipStream_t *st)
     *st = C.st;
     return 0;
 }
-int decode_counter(const char *key, uint64_t *value);      // "decode_*": nlzm_hip_decode.cpp
-int crc_counter(const char *key, uint64_t *value);         // "crc_*": nlzm_hip_crc.cpp
-int range_counter(const char *key, uint64_t *value);       // "range_*": nlzm_hip_range.cpp
-void crc_begin_call();
-int crc_ranges_on(hipStream_t st, const void *d_buf, uint64_t buf_len, uint32_t nranges, const uint64_t *off, const uint64_t *len, uint32_t seed, uint32_t *crc_out);
 }  // namespace nlzm
 
 extern "C" {

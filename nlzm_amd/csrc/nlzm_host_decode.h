@@ -117,6 +117,20 @@ inline size_t stream_length(const Span &in)
     }
 }
 
+// The split of a container by its frame headers: the lengths of the streams that lie back to back from in[0], at most `max` of them,
+// up to the first bytes that are no stream.  Returns how many there are.
+inline size_t split_streams(const Span &in, size_t max, std::vector<uint64_t> &len)
+{
+    len.clear();
+    for (size_t pos = 0; len.size() < max && pos < in.size();) {
+        const size_t l = stream_length(Span{ in.p + pos, in.size() - pos });
+        if (!l) break;
+        len.push_back(l);
+        pos += l;
+    }
+    return len.size();
+}
+
 // (distance, length) of every match, for tests that must know what a stream contains
 struct MatchLog { std::vector<uint32_t> dv, lv; std::vector<uint64_t> at; };      // at: the output offset a match starts at
 

@@ -1,0 +1,113 @@
+// nlzm_host_util.h -- what the library's host files share (the -x hip ones: nlzm_hip.cpp, nlzm_hip_decode.cpp, nlzm_hip_crc.cpp,
+// nlzm_hip_range.cpp; nothing else includes this): the error and buffer scaffolding of the read side's entry points, the per-device
+// record of a call's counters, and THE prototypes of every function that crosses a file boundary -- a changed signature fails to compile.
+#pragma once
+
+#include <hip/hip_runtime.h>
+
+#include <stdarg.h>
+#include <stdint.h>
+#include <stdio.h>
+
+#include <map>
+#include <mutex>
+#include <vector>
+
+#include "../../include/nlzm_hip.h"
+
+namespace nlzm {
+namespace dec { struct StreamArgs; struct StreamResult; }
+namespace crc { struct Args; }
+namespace range { struct Args; }
+
+// nlzm_hip.cpp: the library's error text and its stream (an error if nlzm_hip_init has not succeeded)
+int host_error(int code, const char *text);
+int host_stream(hipStream_t *st);
+// nlzm_decode.hip, nlzm_crc.hip, nlzm_range.hip
+void launch_decode(const void *d_args, void *d_res, uint32_t nstreams, hipStream_t st);
+void launch_split(const void *d_src, unsigned long long len, uint32_t nblocks, unsigned long long *d_block_len, uint32_t *d_bad, hipStream_t st);
+void launch_compare(const void *d_a, const void *d_b, unsigned long long n, unsigned long long *d_first, hipStream_t st);
+void launch_crc(const crc::Args &a, uint32_t max_blocks, hipStream_t st);
+void launch_gather(const range::Args &a, uint32_t max_blocks, hipStream_t st);
+// nlzm_hip_decode.cpp
+void decode_begin_call();                           // a new call: its device time and pass count start at 0
+double decode_call_ms();                            // device time of the call's passes so far
+dec::StreamArgs decode_stream_args(const uint8_t *d_stream, uint64_t len, uint8_t *d_dst, uint64_t cap);
+int decode_run_streams(hipStream_t st, const std::vector<dec::StreamArgs> &args, std::vector<dec::StreamResult> &res);
+int decode_sizes(hipStream_t st, const uint8_t *d_src, const std::vector<uint64_t> &off, const std::vector<uint64_t> &len, std::vector<uint64_t> &raw);
+int decode_split(hipStream_t st, const void *d_src, uint64_t src_len, uint32_t nblocks, const uint64_t *block_len, std::vector<uint64_t> &off, std::vector<uint64_t> &len);
+int decode_split_host(const uint8_t *src, uint64_t src_len, uint32_t nblocks, const uint64_t *block_len, std::vector<uint64_t> &off, std::vector<uint64_t> &len);
+// nlzm_hip_crc.cpp
+void crc_begin_call();
+int crc_ranges_on(hipStream_t st, const void *d_buf, uint64_t buf_len, uint32_t nranges, const uint64_t *off, const uint64_t *len, uint32_t seed, uint32_t *crc_out);
+// nlzm_hip_get_counter's "decode_*", "crc_*" and "range_*": nlzm_hip_decode.cpp, nlzm_hip_crc.cpp, nlzm_hip_range.cpp
+int decode_counter(const char *key, uint64_t *value);
+int crc_counter(const char *key, uint64_t *value);
+int range_counter(const char *key, uint64_t *value);
+
+inline int fail(int code, const char *fmt, ...)
+{
+    char text[512];
+    va_list ap;
+    va_start(ap, fmt);
+    vsnprintf(text, sizeof text, fmt, ap);
+    va_end(ap);
+    return host_error(code, text);
+}
+#ifndef HIPCHK      // (nlzm_hip.cpp keeps its own, tied to its per-thread error text)
+#define HIPCHK(expr)                                                                                                        \
+    do {                                                                                                                    \
+        hipError_t e_ = (expr);                                                                                             \
+        if (e_ != hipSuccess)                                                                                               \
+            return fail(e_ == hipErrorOutOfMemory ? NLZM_HIP_E_NOMEM : NLZM_HIP_E_NODEVICE, "%s failed: %s", #expr, hipGetErrorString(e_)); \
+    } while (0)
+#endif
+
+struct DevBuf {
+    void *p = nullptr;
+    ~DevBuf() { if (p) (void)hipFree(p); }
+    int alloc(size_t bytes) { HIPCHK(hipMalloc(&p, bytes ? bytes : 16)); return 0; }
+    template <class T> T *as() const { return (T *)p; }
+};
+struct Events {
+    hipEvent_t ev[2] = { nullptr, nullptr };
+    ~Events() { for (auto &e : ev) if (e) (void)hipEventDestroy(e); }
+    int create() { for (auto &e : ev) HIPCHK(hipEventCreate(&e)); return 0; }
+};
+
+// One record per device, like the rest of the library's state: what nlzm_hip_get_counter reports of the last call.  The map is guarded, a
+// record is its device's (calls are not re-entrant per device).  No device: one record under -1, which only ever holds zeros.
+template <class T> class PerDevice {
+    std::mutex mu;
+    std::map<int, T> of;
+public:
+    T &here()
+    {
+        int device = -1;
+        (void)hipGetDevice(&device);
+        std::lock_guard<std::mutex> lk(mu);
+        return of[device];
+    }
+};
+
+// One timed launch on `st`: before() queues what the kernel reads, launch() starts it, after() queues what comes back; each but launch()
+// returns a hipError_t.  The stream is synchronised EVEN ON FAILURE: nothing queued before the failure may outlive the host memory the
+// copies name.  ms: the kernel's device time, between two events.
+template <class Before, class Launch, class After>
+int timed_launch(hipStream_t st, const char *what, float *ms, Before before, Launch launch, After after)
+{
+    Events E;
+    if (const int rc = E.create()) return rc;
+    hipError_t e = before();
+    if (e == hipSuccess) e = hipEventRecord(E.ev[0], st);
+    if (e == hipSuccess) { launch(); e = hipGetLastError(); }
+    if (e == hipSuccess) e = hipEventRecord(E.ev[1], st);
+    if (e == hipSuccess) e = after();
+    if (e == hipSuccess) e = hipStreamSynchronize(st);
+    else (void)hipStreamSynchronize(st);
+    if (e == hipSuccess) e = hipEventElapsedTime(ms, E.ev[0], E.ev[1]);
+    if (e != hipSuccess) return fail(NLZM_HIP_E_NODEVICE, "%s launch failed: %s", what, hipGetErrorString(e));
+    return 0;
+}
+
+}  // namespace nlzm

@@ -13,6 +13,7 @@
 // A read outside a range that leaves the mapping ends the harness with SIGSEGV: this is host code, which is where faults belong.
 #define NLZM_SIM 1
 #include "../../nlzm_amd/csrc/nlzm_crc.h"
+#include "../../nlzm_amd/csrc/nlzm_read_plan.h"
 
 #include <stdio.h>
 #include <stdlib.h>
@@ -34,18 +35,19 @@ void entry(void *arg)
     else crc::segments_role(P->a, P->threads, (unsigned long long)xw::block_index() * (P->threads / 64) + xw::wave(), (unsigned long long)xw::sim().nblocks * (P->threads / 64));
 }
 
-// the CRCs of k ranges of buf, as the library's host side sets a call up (nlzm_hip_crc.cpp: crc_ranges_on)
-std::vector<uint32_t> run(const uint8_t *buf, const std::vector<unsigned long long> &off, const std::vector<unsigned long long> &len, uint32_t seed, uint32_t threads,
+// the CRCs of k ranges of the buf_len bytes at buf, from the table the library's host side hands its launch (nlzm_read_plan.h: crc::SegTable)
+std::vector<uint32_t> run(const uint8_t *buf, uint64_t buf_len, const std::vector<uint64_t> &off, const std::vector<uint64_t> &len, uint32_t seed, uint32_t threads,
                           uint32_t blocks)
 {
     const uint32_t k = (uint32_t)off.size();
-    std::vector<unsigned long long> o(off), l(len), seg0(k + 1);
-    o.push_back(0); l.push_back(0);
-    unsigned long long nsegs = 0;
-    for (uint32_t i = 0; i < k; i++) { seg0[i] = nsegs; nsegs += (len[i] + crc::kSegment - 1) / crc::kSegment; }
-    seg0[k] = nsegs;
+    crc::SegTable T;
+    char why[512];
+    if (T.make(buf_len, k, off.data(), len.data(), crc::kSegment, ErrText{ why, sizeof why })) { fprintf(stderr, "crc_sim: %s\n", why); exit(2); }
+    const unsigned long long nsegs = T.nsegs;
     std::vector<uint32_t> part(nsegs + 1, 0xDEADBEEFu), out(k, 0xDEADBEEFu);
-    Launch P{ crc::Args{ buf, o.data(), l.data(), seg0.data(), part.data(), out.data(), k, seed, nsegs }, threads, false };
+    Launch P{ crc::Args{}, threads, false };
+    P.a.buf = buf; P.a.part = part.data(); P.a.out = out.data(); P.a.seed = seed;
+    T.point(P.a, T.words.data());
     if (nsegs) {
         std::vector<unsigned long long> lds(blocks, sizeof(crc::Lds));
         xw::launch(blocks, threads, lds.data(), entry, &P);
@@ -101,23 +103,27 @@ int main(int argc, char **argv)
             memset(g.lo, 0xA5, room);
             uint8_t *front = g.lo + align;
             if (n) memcpy(front, data.data() + start, n);
-            const uint32_t c0 = run(front, { 0 }, { n }, seed, threads, blocks)[0];
+            const uint32_t c0 = run(front, n, { 0 }, { n }, seed, threads, blocks)[0];
             memset(g.lo, 0x5A, room);
             uint8_t *back = g.hi - n;
             if (n) memcpy(back, data.data() + start, n);
-            const uint32_t c1 = run(back, { 0 }, { n }, seed, threads, blocks)[0];
+            const uint32_t c1 = run(back, n, { 0 }, { n }, seed, threads, blocks)[0];
             printf("%08X %08X\n", c0, c1);
         } else if (kind[0] == 'R') {
             unsigned long long bytes;
             unsigned k;
             if (fscanf(f, "%llu %u", &bytes, &k) != 2 || bytes > data.size() || bytes > room) return 2;
-            std::vector<unsigned long long> off(k), len(k);
-            for (unsigned i = 0; i < k; i++) if (fscanf(f, "%llu %llu", &off[i], &len[i]) != 2 || off[i] > bytes || len[i] > bytes - off[i]) return 2;
+            std::vector<uint64_t> off(k), len(k);
+            for (unsigned i = 0; i < k; i++) {
+                unsigned long long o, l;
+                if (fscanf(f, "%llu %llu", &o, &l) != 2 || o > bytes || l > bytes - o) return 2;
+                off[i] = o; len[i] = l;
+            }
             Guarded r;
             r.make(bytes);
             if ((size_t)(r.hi - r.lo) != bytes) return 2;
             memcpy(r.lo, data.data(), bytes);
-            const std::vector<uint32_t> c = run(r.lo, off, len, 0, 128, 3);
+            const std::vector<uint32_t> c = run(r.lo, bytes, off, len, 0, 128, 3);
             for (unsigned i = 0; i < k; i++) printf("%08X%s", c[i], i + 1 < k ? " " : "\n");
         } else return 2;
     }

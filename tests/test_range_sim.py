@@ -1,6 +1,7 @@
 """CPU suite: what the range reader adds to the device code, compiled for the host with every GPU lane a fiber
 (tests/host_sim/range_sim.cpp): the decoder role's prefix mode (nlzm_amd/csrc/nlzm_decode.h, dec::kPrefix) against the host decoder, and
-the gather role (nlzm_amd/csrc/nlzm_range.h) against memcpy.
+the gather role (nlzm_amd/csrc/nlzm_range.h) against memcpy; and the plan the library's host side makes of a call
+(nlzm_amd/csrc/nlzm_read_plan.h: the same text the library and the command line compile), carried out with memcpy.
 
 Prefix mode: a decode with the flag ends successfully at `cap`; the harness gives the destination exactly cap bytes, misaligned by
 cap % 16, between two canary regions, and holds out_len, every byte, and the role's ring / memory byte counters against what the host
@@ -79,6 +80,7 @@ def runs(tmp_path_factory):
     f = d / "mixed.txt"
     f.write_text("M 11 300\nM 12 300\nM 13 0\n")
     jobs.append((("mixed",), [SIM, "gather", f]))
+    jobs.append((("plan",), [SIM, "plan"]))
     ex = ThreadPoolExecutor(WORKERS)
     futs = {key: ex.submit(sh, cmd) for key, cmd in jobs}
     yield {"futs": futs, "raws": raws, "caps": caps, "G": G}
@@ -158,3 +160,18 @@ def test_gather_300_pieces_in_one_launch(runs):
     rows = [tuple(map(int, re.findall(r"=(\d+)", l))) for l in out.splitlines() if l.startswith("pieces=")]
     assert [r[0] for r in rows] == [300, 300, 0]
     assert all(empty >= 20 and big >= 1 for k, empty, big, _ in rows[:2])
+
+
+def test_plan_of_every_range_and_every_pair(runs):
+    """The library's make_plan and pack_pieces on a container of six blocks of raw lengths 5, 0, 7, 3, 0, 4: every single range inside its 19
+    bytes (210, the empty ones and off == 19 among them) and every ordered pair of them (44,100).  Per plan the harness holds need[b]
+    (the furthest byte any range wants of b; 0 for untouched and empty blocks), direct (exactly one range uses the block and starts at or
+    before its first byte), scratch (the sum of need over the needed non-direct blocks) and the piece list (none of a direct block) against
+    the definitions written out block by block, then carries the plan out -- every needed block's first need[b] bytes copied to place[b],
+    the packed pieces moved -- and compares the destination with the slices back to back, destination and scratch between canaries.
+    Seven of the plans, (3, 10) + (0, 19) among them, have the real gather role move the packed pieces in the fiber simulator.  The
+    errors: E_ARG for off = 2^64 - 1, len = 2, for off = 20, len = 0 and for raw lengths that wrap 64 bits; E_CAPACITY for dst_cap one
+    below the sum (and none for dst_cap equal to it).  Half a second."""
+    out = ok(runs, ("plan",))
+    got = tuple(map(int, re.search(r"plans=(\d+) role_plans=(\d+) errors=(\d+)", out).groups()))
+    assert got == (210 + 210 * 210, 7, 4), got
