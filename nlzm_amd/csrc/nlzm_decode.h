@@ -411,5 +411,33 @@ XW_FN void decode_role(const StreamArgs &A, StreamResult *res)
     }
 }
 
+// ---- the split of a container -------------------------------------------------------------------------------------------------------
+// stream_length (nlzm_host_decode.h) for nblocks streams back to back: ONE lane follows the sizes the frame headers carry (no cross-lane
+// operation: the caller picks the lane).  block_len[i] = 0 and *bad = 1 + i when stream i is malformed or cut off; *bad = 0 and every
+// length when all nblocks are there.  Reads stay inside [src, src + len); every step moves forward by at least 28 bytes or ends.
+// tests/host_sim/decode_sim.cpp (split) holds it to nlzm_host::split_streams, flush against a page that may not be read.
+XW_FN void split_walk(const uint8_t *__restrict__ src, unsigned long long len, uint32_t nblocks, unsigned long long *__restrict__ block_len,
+                      uint32_t *__restrict__ bad)
+{
+    auto be32 = [&](unsigned long long p) { return ((uint32_t)src[p] << 24) | ((uint32_t)src[p + 1] << 16) | ((uint32_t)src[p + 2] << 8) | src[p + 3]; };
+    unsigned long long at = 0;
+    *bad = 0;
+    for (uint32_t i = 0; i < nblocks; i++) {
+        unsigned long long pos = at + 4, end = 0;
+        if (len - at < 8 || at > len) { *bad = 1 + i; }
+        else for (;;) {
+            if (pos + 4 > len) { *bad = 1 + i; break; }
+            if (!be32(pos)) { end = pos + 4; break; }
+            if (pos + 12 > len) { *bad = 1 + i; break; }
+            const uint32_t nb = be32(pos + 4), nr = be32(pos + 8);
+            if (nb < 12 || nr < 16 || pos + (unsigned long long)nb + nr > len) { *bad = 1 + i; break; }
+            pos += (unsigned long long)nb + nr;
+        }
+        if (!end) { for (; i < nblocks; i++) block_len[i] = 0; return; }
+        block_len[i] = end - at;
+        at = end;
+    }
+}
+
 }  // namespace dec
 }  // namespace nlzm

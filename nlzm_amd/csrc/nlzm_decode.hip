@@ -26,30 +26,12 @@ __global__ __launch_bounds__(64) void decode_kernel(const dec::StreamArgs *__res
     dec::decode_role(a, res + blockIdx.x);
 }
 
-// stream_length (nlzm_host_decode.h) for nblocks streams back to back in device memory: one lane follows the sizes the frame headers
-// carry.  block_len[i] = 0 and *bad = 1 + i when stream i is malformed or cut off.  Reads stay inside [src, src + len).
+// the split of a container in device memory (dec::split_walk, nlzm_decode.h): one lane follows the sizes the frame headers carry
 __global__ __launch_bounds__(64) void split_kernel(const uint8_t *__restrict__ src, unsigned long long len, uint32_t nblocks,
                                                    unsigned long long *__restrict__ block_len, uint32_t *__restrict__ bad)
 {
     if (threadIdx.x || blockIdx.x) return;
-    auto be32 = [&](unsigned long long p) { return ((uint32_t)src[p] << 24) | ((uint32_t)src[p + 1] << 16) | ((uint32_t)src[p + 2] << 8) | src[p + 3]; };
-    unsigned long long at = 0;
-    *bad = 0;
-    for (uint32_t i = 0; i < nblocks; i++) {
-        unsigned long long pos = at + 4, end = 0;
-        if (len - at < 8 || at > len) { *bad = 1 + i; }
-        else for (;;) {
-            if (pos + 4 > len) { *bad = 1 + i; break; }
-            if (!be32(pos)) { end = pos + 4; break; }
-            if (pos + 12 > len) { *bad = 1 + i; break; }
-            const uint32_t nb = be32(pos + 4), nr = be32(pos + 8);
-            if (nb < 12 || nr < 16 || pos + (unsigned long long)nb + nr > len) { *bad = 1 + i; break; }
-            pos += (unsigned long long)nb + nr;
-        }
-        if (!end) { for (; i < nblocks; i++) block_len[i] = 0; return; }
-        block_len[i] = end - at;
-        at = end;
-    }
+    dec::split_walk(src, len, nblocks, block_len, bad);
 }
 
 // verify: *first = min(*first, the first offset below n at which a and b differ).  Sixteen bytes per lane and step (one 16-byte load

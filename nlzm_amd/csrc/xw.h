@@ -9,7 +9,10 @@
 //     that the role logic can be checked against the oracle on a machine without a GPU.
 //
 // Contract for role code: cross-lane operations are called in wave-uniform control flow (all live
-// lanes of the wave reach the same call); spin-waits call xw::pause() between polls.
+// lanes of the wave reach the same call); spin-waits call xw::pause() between polls.  A result that depends on the value of a lane that
+// has left the role (returned) is undefined in BOTH builds: ballot's bits of such lanes are 0 and readfirst picks the first live lane,
+// but a readlane, shuffle, scan or lane_below whose source is such a lane may return anything on the device, and the simulator ends the
+// run ("a live lane reads an exited lane").  tests/xw_probe holds both builds to tests/xw_model.py, primitive by primitive.
 #pragma once
 
 #include <stdint.h>

@@ -5,9 +5,15 @@
 //   decode_sim blocks  <container> <out> <given>    k streams back to back as k workgroups of one launch; given = 1: block and raw
 //                                                   lengths from the host decoder, 0: split by frame hopping + a size-only launch first
 //   decode_sim mutants <stream> <seed> <flips> <shard> <nshards>    damaged copies of the stream: role and host decoder must agree
+//   decode_sim split   <container>                  dec::split_walk (the body of the device's split kernel) against nlzm_host::split_streams:
+//                                                   the container cut at every length, and with edited frame headers, for 1 .. 7 blocks
 //
-// Every buffer the role sees lies between two canary regions, at an address that is deliberately not aligned; the canaries are
-// checked after every launch.
+// Every buffer the role sees lies inside a mapping of its own between two PROT_NONE pages, and what is left of the mapping around it is
+// a canary that is checked after every launch.  decode / blocks: at an address that is deliberately not aligned, canaries on both
+// sides.  mutants / split: the role's promise that reads stay inside [src, src + len) and writes inside [dst, dst + cap) is tested by
+// the pages themselves -- every damaged stream is run once with source and destination flush against the page BEHIND them and once
+// starting right behind the page IN FRONT (the canary is then on the side where no page can sit).  A read or write outside is a SIGSEGV of
+// the harness: this is host code, which is where faults belong.
 #define NLZM_SIM 1
 #include "../../nlzm_amd/csrc/nlzm_decode.h"
 #include "../../nlzm_amd/csrc/nlzm_host_decode.h"
@@ -15,6 +21,8 @@
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
+#include <sys/mman.h>
+#include <unistd.h>
 
 #include <map>
 #include <string>
@@ -27,22 +35,33 @@ namespace {
 constexpr size_t kCanary = 4096;
 constexpr uint8_t kPoison = 0xA5;
 
-// a buffer of n bytes at a chosen misalignment between two canaries
+// a buffer of n bytes between two PROT_NONE pages: kMid at a chosen misalignment with canaries on both sides, kFront starting right behind
+// the page in front, kBack with its last byte flush against the page behind; whatever else the pages enclose is canary
+enum Place { kMid, kFront, kBack };
 struct Guarded {
-    std::vector<uint8_t> mem;
-    size_t off = 0, n = 0;
-    void make(size_t bytes, size_t misalign, uint8_t fill)
+    uint8_t *map = nullptr, *lo = nullptr, *hi = nullptr, *q = nullptr;      // [lo, hi): readable and writable; q: the buffer
+    size_t map_len = 0, n = 0;
+    Guarded() = default;
+    Guarded(const Guarded &) = delete;
+    Guarded &operator=(const Guarded &) = delete;
+    ~Guarded() { if (map) munmap(map, map_len); }
+    void make(size_t bytes, size_t misalign, uint8_t fill, Place place = kMid)
     {
-        n = bytes;
-        mem.assign(2 * kCanary + bytes + 64, kPoison);
-        off = kCanary + ((64 - ((uintptr_t)mem.data() + kCanary) % 64) % 64) + misalign;
-        memset(mem.data() + off, fill, bytes);
+        if (map) { munmap(map, map_len); map = nullptr; }
+        const size_t pg = (size_t)sysconf(_SC_PAGESIZE), room = (bytes + 2 * kCanary + 64 + pg - 1) / pg * pg;
+        map_len = room + 2 * pg;
+        map = (uint8_t *)mmap(nullptr, map_len, PROT_READ | PROT_WRITE, MAP_PRIVATE | MAP_ANONYMOUS, -1, 0);
+        if (map == MAP_FAILED || mprotect(map, pg, PROT_NONE) || mprotect(map + pg + room, pg, PROT_NONE)) { fprintf(stderr, "decode_sim: no guarded buffer\n"); exit(2); }
+        lo = map + pg; hi = lo + room; n = bytes;
+        memset(lo, kPoison, room);
+        q = place == kFront ? lo : place == kBack ? hi - bytes : lo + kCanary + misalign;
+        memset(q, fill, bytes);
     }
-    uint8_t *p() { return mem.data() + off; }
+    uint8_t *p() { return q; }
     bool intact() const
     {
-        for (size_t i = 0; i < off; i++) if (mem[i] != kPoison) return false;
-        for (size_t i = off + n; i < mem.size(); i++) if (mem[i] != kPoison) return false;
+        for (const uint8_t *c = lo; c < q; c++) if (*c != kPoison) return false;
+        for (const uint8_t *c = q + n; c < hi; c++) if (*c != kPoison) return false;
         return true;
     }
 };
@@ -179,31 +198,33 @@ int cmd_blocks(int argc, char **argv)
     return 0;
 }
 
-// one damaged stream through both decoders; returns 0 when they agree
+// one damaged stream through both decoders, with source and destination against the page behind them and behind the page in front; returns 0
+// when role and host decoder agree both times
 int one_mutant(const std::vector<uint8_t> &s, const char *what, size_t idx, long long cap_delta, unsigned *accepted)
 {
     std::vector<uint8_t> want;
     uint32_t hb = 0, fb = 0;
     const int hrc = nlzm_host::decode_stream(nlzm_host::Span{ s.data(), s.size() }, want, &hb, &fb);
-    Guarded src, dst;
-    src.make(s.size(), idx % 4, 0);
-    if (s.size()) memcpy(src.p(), s.data(), s.size());
     const size_t cap = (size_t)((long long)want.size() + cap_delta);
-    dst.make(cap, idx % 16, 0x5C);
-    LaunchPack P;
-    P.a.push_back(dec::StreamArgs{ src.p(), s.size(), dst.p(), cap, ~0ull });
-    run(P);
-    const dec::StreamResult &r = P.r[0];
-    if (!src.intact() || !dst.intact()) { printf("FAIL %s %zu: canary damaged\n", what, idx); return 1; }
-    if (cap_delta < 0) {
-        if (hrc || r.rc != dec::kErrCapacity) { printf("FAIL %s %zu: dst_cap one short gives rc %d\n", what, idx, r.rc); return 1; }
-        return 0;
+    for (Place place : { kBack, kFront }) {
+        const char *where = place == kBack ? "against the page behind" : "behind the page in front";
+        Guarded src, dst;
+        src.make(s.size(), 0, 0, place);
+        if (s.size()) memcpy(src.p(), s.data(), s.size());
+        dst.make(cap, 0, 0x5C, place);
+        LaunchPack P;
+        P.a.push_back(dec::StreamArgs{ src.p(), s.size(), dst.p(), cap, ~0ull });
+        run(P);
+        const dec::StreamResult &r = P.r[0];
+        if (!src.intact() || !dst.intact()) { printf("FAIL %s %zu (%s): canary damaged\n", what, idx, where); return 1; }
+        if (cap_delta < 0) {
+            if (hrc || r.rc != dec::kErrCapacity) { printf("FAIL %s %zu (%s): dst_cap one short gives rc %d\n", what, idx, where, r.rc); return 1; }
+            continue;
+        }
+        if ((r.rc != 0) != (hrc != 0)) { printf("FAIL %s %zu (%s): role rc %d (detail %u), host decoder rc %d\n", what, idx, where, r.rc, r.detail, hrc); return 1; }
+        if (!hrc && (r.out_len != want.size() || (want.size() && memcmp(dst.p(), want.data(), want.size())))) { printf("FAIL %s %zu (%s): accepted, bytes differ\n", what, idx, where); return 1; }
     }
-    if ((r.rc != 0) != (hrc != 0)) { printf("FAIL %s %zu: role rc %d (detail %u), host decoder rc %d\n", what, idx, r.rc, r.detail, hrc); return 1; }
-    if (!hrc) {
-        (*accepted)++;
-        if (r.out_len != want.size() || (want.size() && memcmp(dst.p(), want.data(), want.size()))) { printf("FAIL %s %zu: accepted, bytes differ\n", what, idx); return 1; }
-    }
+    if (!hrc && cap_delta >= 0) (*accepted)++;
     return 0;
 }
 
@@ -251,10 +272,80 @@ int cmd_mutants(int argc, char **argv)
     return 0;
 }
 
+// dec::split_walk on the `len` bytes at p (which lie flush against a PROT_NONE page) against the host's split of the same span
+int one_split(const uint8_t *p, size_t len, uint32_t nblocks, const char *what, size_t idx)
+{
+    std::vector<uint64_t> hl;
+    const size_t found = nlzm_host::split_streams(nlzm_host::Span{ p, len }, nblocks, hl);
+    unsigned long long got[8];
+    for (auto &g : got) g = 0xA5A5A5A5A5A5A5A5ull;
+    uint32_t bad = 0xA5A5A5A5u;
+    dec::split_walk(p, len, nblocks, got, &bad);
+    const uint32_t want_bad = found < nblocks ? (uint32_t)found + 1 : 0;
+    bool ok = bad == want_bad && got[nblocks] == 0xA5A5A5A5A5A5A5A5ull;
+    for (uint32_t i = 0; i < nblocks; i++) ok = ok && got[i] == (i < found ? hl[i] : 0);
+    if (!ok) {
+        printf("FAIL split %s %zu, %u blocks: bad %u (host: %u), lengths", what, idx, nblocks, bad, want_bad);
+        for (uint32_t i = 0; i < nblocks; i++) printf(" %llu/%llu", got[i], (unsigned long long)(i < found ? hl[i] : 0));
+        printf("\n");
+        return 1;
+    }
+    return 0;
+}
+
+int cmd_split(int argc, char **argv)
+{
+    (void)argc;
+    const std::vector<uint8_t> blob = slurp(argv[2]);
+    std::vector<uint64_t> lens;
+    const size_t k = nlzm_host::split_streams(nlzm_host::Span{ blob.data(), blob.size() }, 64, lens);
+    if (k != 5) { printf("FAIL: the container holds %zu streams, not five\n", k); return 1; }
+    Guarded g;
+    g.make(blob.size(), 0, 0, kBack);
+    uint8_t *hi = g.p() + blob.size();
+    size_t cuts = 0, edits = 0, rejected = 0;
+    // cut at every length, the cut's last byte against the page
+    for (size_t len = 0; len <= blob.size(); len++) {
+        if (len) memcpy(hi - len, blob.data(), len);
+        for (uint32_t nb = 1; nb <= 7; nb++) if (one_split(hi - len, len, nb, "cut", len)) return 1;
+        cuts++;
+    }
+    // edited frame headers: the first frame of the third stream (one frame) and of the fifth (several), and the fifth's second frame
+    std::vector<size_t> heads;
+    size_t at = 0;
+    for (size_t i = 0; i < k; i++) {
+        if (i == 2 || i == 4) heads.push_back(at + 4);
+        if (i == 4) { const size_t second = at + 4 + nlzm_host::be32(&blob[at + 8]) + nlzm_host::be32(&blob[at + 12]); if (second + 12 <= at + lens[i] && nlzm_host::be32(&blob[second])) heads.push_back(second); }
+        at += lens[i];
+    }
+    if (heads.size() != 3) { printf("FAIL: the fifth stream has one frame only\n"); return 1; }
+    for (size_t h : heads) {
+        const uint32_t nb0 = nlzm_host::be32(&blob[h + 4]), nr0 = nlzm_host::be32(&blob[h + 8]);
+        const uint32_t over = (uint32_t)(blob.size() - h - nb0) + 1;         // nb + nr runs one byte over the end
+        const struct { const char *what; uint32_t nb, nr; } E[] = { { "nb=0", 0, nr0 }, { "nb=11", 11, nr0 }, { "nb=0xFFFFFFFF", 0xFFFFFFFFu, nr0 }, { "nr=15", nb0, 15 },
+            { "nb+nr over the end", nb0, over }, { "nb+nr to the end exactly", nb0, over - 1 }, { "nb=nr=0xFFFFFFFF", 0xFFFFFFFFu, 0xFFFFFFFFu }, { "num_ops=0", nb0, nr0 } };
+        for (const auto &e : E) {
+            std::vector<uint8_t> m = blob;
+            put_be32(m, h + 4, e.nb); put_be32(m, h + 8, e.nr);
+            if (!strcmp(e.what, "num_ops=0")) put_be32(m, h, 0);
+            memcpy(hi - m.size(), m.data(), m.size());
+            std::vector<uint64_t> hl;
+            if (nlzm_host::split_streams(nlzm_host::Span{ m.data(), m.size() }, 5, hl) < 5) rejected++;
+            for (uint32_t nb = 1; nb <= 7; nb++) if (one_split(hi - m.size(), m.size(), nb, e.what, h)) return 1;
+            edits++;
+        }
+    }
+    if (!g.intact()) { printf("FAIL: canary damaged\n"); return 1; }
+    printf("split: streams=%zu bytes=%zu cuts=%zu edits=%zu rejected=%zu\n", k, blob.size(), cuts, edits, rejected);
+    printf("decode_sim: OK\n");
+    return 0;
+}
+
 }  // namespace
 
 int main(int argc, char **argv)
 {
+    if (argc == 3 && !strcmp(argv[1], "split")) return cmd_split(argc, argv);
     if (argc >= 4 && !strcmp(argv[1], "decode")) return cmd_decode(argc, argv);
     if (argc == 5 && !strcmp(argv[1], "blocks")) return cmd_blocks(argc, argv);
     if (argc == 7 && !strcmp(argv[1], "mutants")) return cmd_mutants(argc, argv);

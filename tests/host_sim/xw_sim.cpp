@@ -3,7 +3,9 @@
 // TEST HARNESS ONLY.  Every lane of every wave is a fiber with its own stack; a wave's lanes run one after the
 // other until each has reached the same cross-lane operation (or a pause, a workgroup barrier, or its end), then
 // the operation is completed for all of them.  Role code therefore runs with exactly the control flow it has on the
-// GPU, including divergence, and a cross-lane operation reached by only part of a wave is reported as an error.
+// GPU, including divergence, and a cross-lane operation reached by only part of a wave is reported as an error.  So is a readlane,
+// shuffle or scan in which a live lane's source is a lane that has left the role: xw.h leaves that value undefined in both builds, and
+// the simulator does not hand out the exited fiber's last argument in its place.
 #define NLZM_SIM 1
 #include "../../nlzm_amd/csrc/xw.h"
 
@@ -104,12 +106,17 @@ static bool run_wave(Wave &w)
                 }
                 if (src == 64) { for (uint32_t l = 0; l < 64; l++) if (w.f[l].state == kColl) { src = l; break; } }   // readfirstlane
                 if (src >= 64) fail("readlane of lane >= 64", w);
-                const unsigned long long v = w.f[src].in;       // (an exited lane's last value, as on the hardware: undefined there)
+                // (readfirst picked a live lane; a NAMED lane that has left the role holds nothing defined, in either build: xw.h's contract)
+                if (w.f[src].state != kColl) fail("a live lane reads an exited lane (readlane)", w);
+                const unsigned long long v = w.f[src].in;
                 for (uint32_t l = 0; l < 64; l++) w.f[l].out = v;
             } else if (kind == cShfl) {
                 unsigned long long tmp[64];
                 for (uint32_t l = 0; l < 64; l++) tmp[l] = w.f[l].in;
-                for (uint32_t l = 0; l < 64; l++) if (w.f[l].state == kColl) w.f[l].out = tmp[w.f[l].src & 63u];
+                for (uint32_t l = 0; l < 64; l++) if (w.f[l].state == kColl) {
+                    if (w.f[w.f[l].src & 63u].state != kColl) fail("a live lane reads an exited lane (shuffle or scan)", w);
+                    w.f[l].out = tmp[w.f[l].src & 63u];
+                }
             }
             for (uint32_t l = 0; l < 64; l++) if (w.f[l].state == kColl) w.f[l].state = kReady;
             continue;

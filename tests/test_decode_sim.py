@@ -6,11 +6,15 @@ The simulator decodes ~60,000 rANS symbols per second on one core (a symbol is f
 literal-heavy case costs the most: random_100k_w15 5 s, dups_600k_w20 12 s, dups_400k_w16 9 s, xml_400k_w19 / runs_300k_w18 /
 text_200k_w15 3 - 5 s, the rest under a second; size-only mode costs the same again; a ring-edge input 4 - 8 s; a mutant of
 random_100k_w15 up to 5 s (most are rejected early).  All runs (one process each) are started together when the first test asks
-for one, the longest first, and every test takes the result of its own run: 86 s on eight cores from a clean tree (12 s of it the three
-builds of the harness, made beside each other; 555 s of CPU time in all), measured with nothing else running.
+for one, the longest first, and every test takes the result of its own run: 130 s on eight cores with the harnesses built (the three
+builds, made beside each other, add 12 s; 820 s of CPU time in all -- every damaged stream is decoded twice), measured with nothing else running.
 
 Mutants run in a UBSan build; AddressSanitizer does not follow the fibers' hand-switched stacks (it reports the first switch), so
-instead every buffer the role sees lies, misaligned on purpose, between two 4 KiB canary regions that are checked after every launch."""
+instead every buffer the role sees lies in a mapping of its own between two PROT_NONE pages, and what the pages enclose beside it is a
+canary that is checked after every launch.  Well-formed streams are decoded at addresses that are misaligned on purpose, canaries on
+both sides; every damaged stream is decoded twice, source and destination flush against the page behind them and starting right behind
+the page in front, so that a read outside [src, src + len) or a write outside [dst, dst + cap) ends the harness with SIGSEGV.  The
+split of a container (dec::split_walk, the body of the device's split kernel) runs in the same harness, against the host's."""
 import hashlib
 import json
 import os
@@ -38,6 +42,7 @@ EDGES = [-1, 0, 1]                                         # D - R
 # (stream, single-bit flips, processes the list is dealt to)
 MUTANTS = [("tiny_1000", 200, 1), ("chunk_plus1", 200, 4), ("random_100k_w15", 100, 10)]
 BLOCKS_K = 5
+SPLIT = ["empty", "one_byte", "tiny_1000", "under_2k", "chunk_plus1"]
 
 
 def sha(b):
@@ -88,6 +93,7 @@ def runs(tmp_path_factory):
     bdata, branges = blocks_input()
     (d / "blocks.nlzm").write_bytes(b"".join(oracle_py.compress(bdata[lo:hi], 18) for lo, hi in branges))
 
+    (d / "split.nlzm").write_bytes(b"".join(streams[n] for n in SPLIT))
     jobs = []                                              # (key, command), the longest first
     for n, flips, parts in MUTANTS:
         if n == "random_100k_w15":
@@ -106,6 +112,7 @@ def runs(tmp_path_factory):
             jobs += [(("mutants", n, s), [SIM_SAN, "mutants", d / f"{n}.nlzm", 7, flips, s, parts]) for s in range(parts)]
     for n in HEX:
         jobs.append((("hex", n), [SIM, "decode", d / f"{n}.hex.nlzm", d / f"{n}.hex.out"]))
+    jobs.append((("split",), [SIM_SAN, "split", d / "split.nlzm"]))
     ex = ThreadPoolExecutor(WORKERS)
     futs = {key: ex.submit(sh, cmd) for key, cmd in jobs}
     yield {"futs": futs, "dir": d, "streams": streams, "inputs": inputs, "ring": ring, "edge": edge, "blocks": (bdata.tobytes(), branges)}
@@ -206,3 +213,15 @@ def test_mutants_agree_with_host_decoder(runs, name, flips, parts):
         m = re.search(r"mutants=(\d+) ran=(\d+)", out)
         total, ran = int(m.group(1)), ran + int(m.group(2))
     assert total == ran == flips + 16 + 4 + 5 + 1
+
+
+def test_split_walk_agrees_with_the_host_split(runs):
+    """dec::split_walk, which the device's split kernel runs in one lane, against nlzm_host::split_streams: a container of five small streams cut
+    at EVERY length from 0 to its end, each cut with its last byte flush against a PROT_NONE page, walked for 1 .. 7 blocks -- the lengths
+    found and bad = found + 1 are the host's; then header edits of three frames (nb 0, 11 and 0xFFFFFFFF, nr 15, a sum that runs over the end
+    by one byte and one that ends exactly there, both sizes 0xFFFFFFFF, a terminator in a frame's place) held to the host's verdict likewise.
+    Every failure exit of the walk is taken; a read outside the span is a SIGSEGV of the harness."""
+    out = ok(runs, ("split",))
+    m = re.search(r"split: streams=5 bytes=(\d+) cuts=(\d+) edits=(\d+) rejected=(\d+)", out)
+    size = sum(len(runs["streams"][n]) for n in SPLIT)
+    assert m and int(m.group(1)) == size and int(m.group(2)) == size + 1 and int(m.group(3)) == 24 and int(m.group(4)) >= 12

@@ -219,3 +219,66 @@ def test_binding_and_command_line(box, tmp_path):
     assert r.returncode == 0, r.stdout + r.stderr
     assert out.read_bytes() == b"".join(want)
     assert "CRC32 ok (3 of 5 blocks read in full)" in r.stdout, r.stdout    # blocks 0, 1, 4, 5, 6 read; 0, 4 and 5 to their ends
+
+
+# ---- the split of the container on the device (split_kernel, dec::split_walk) against the host's walk -------------------------------------
+# nlzm_hip_decompress_blocks_dev without lengths hops over the frame headers in device memory; nlzm_hip_decompress_blocks on host buffers
+# splits with nlzm_host::split_streams.  Wrong ARGUMENTS over intact bytes: nothing here is a damaged stream.  Nothing can wait: the walk is
+# one lane, and every step moves forward by at least 28 bytes or ends.
+
+def split_both(box, nblocks, src_len):
+    """the two entries on the same bytes and arguments -> [(rc, last error, decode passes, dst_len, raw lengths, the destination)] for dev, host"""
+    lib, cap, out = box.lib, box.total, []
+    host_src = np.frombuffer(box.blob, dtype=np.uint8)
+    for dev in (True, False):
+        raw, n = (C.c_uint64 * nblocks)(*([12345] * nblocks)), C.c_uint64(12345)
+        if dev:
+            d = torch.full((cap + 64,), CANARY, dtype=torch.uint8, device="cuda:0")
+            torch.cuda.synchronize()
+            rc = lib.nlzm_hip_decompress_blocks_dev(box.d_src.data_ptr(), src_len, nblocks, None, None, d.data_ptr(), cap, raw, C.byref(n))
+        else:
+            h = np.full(cap + 64, CANARY, dtype=np.uint8)
+            rc = lib.nlzm_hip_decompress_blocks(host_src.ctypes.data, src_len, nblocks, None, None, h.ctypes.data, cap, raw, C.byref(n))
+        err = lib.nlzm_hip_last_error().decode() if rc else ""
+        passes = box.gpu.counter("decode_passes")
+        if dev:
+            torch.cuda.synchronize()
+            h = d.cpu().numpy()
+        out.append((rc, err, passes, int(n.value), list(raw), h.tobytes()))
+    return out
+
+
+def test_split_on_the_device_is_the_hosts(box):
+    """nblocks = K: the outputs are equal (and the inputs); fewer blocks: whatever the host entry does, code and bytes; more blocks than there
+    are: both name block K + 1"""
+    for nblocks in list(range(1, K + 1)) + [K + 1, K + 3]:
+        dev, host = split_both(box, nblocks, len(box.blob))
+        assert dev == host, (nblocks, dev[:5], host[:5])
+        rc, err, passes, n, raw, dst = dev
+        if nblocks <= K:
+            want = b"".join(box.blocks[:nblocks])
+            assert rc == 0 and n == len(want) and raw == box.raws[:nblocks] and dst[:n] == want and set(dst[n:]) == {CANARY}, nblocks
+            assert passes == 2                                           # the size pass, then the decode
+        else:
+            assert rc == E_FORMAT and f"block {K + 1} of {nblocks} " in err and passes == 0, (nblocks, rc, err, passes)
+            assert raw == [12345] * nblocks and n == 12345 and set(dst) == {CANARY}
+
+
+def test_split_of_a_cut_container(box):
+    """src_len cut inside three blocks -- the first (several frames), the empty one, the last -- at offsets round the header's and a frame header's
+    fields, and at the block's last four bytes and last byte: both entries return the same code and name the same block, which is the first
+    block that the bytes do not hold in full, and neither launches a decode"""
+    cstart = [sum(box.lens[:i]) for i in range(K + 1)]
+    seen = set()
+    for j in (0, 2, K - 1):
+        for c in (0, 1, 3, 4, 7, 8, 11, 12, 15, 16, 27, box.lens[j] - 4, box.lens[j] - 1):
+            src_len = cstart[j] + c
+            dev, host = split_both(box, K, src_len)
+            assert dev == host, (j, c, dev[:5], host[:5])
+            rc, err, passes, n, raw, dst = dev
+            first_cut = next(i for i in range(K) if cstart[i + 1] > src_len)       # (c may reach past a short block: the empty one is 8 bytes)
+            assert rc == E_FORMAT and f"block {first_cut + 1} of {K} " in err and passes == 0, (j, c, rc, err, passes)
+            assert set(dst) == {CANARY}
+            seen.add(first_cut)
+    assert seen == {0, 2, 3, K - 1}
+    assert box.lens[0] > 100_000 and box.lens[2] == 8
