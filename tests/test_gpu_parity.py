@@ -234,6 +234,51 @@ def test_rans_frames_stage(gpu):
     assert got == want
 
 
+def rans_stage_frames():
+    """Frames for rans_frames_kernel beyond the captured ones: symbol counts 1 .. 8 (the states' start index ((n-1-k) & ~3) + k for every k and n mod 4),
+    around 256 and 512 (the 256-wide scan of the pushed words and its carry) and 1,027; per count a frame in which no symbol pushes a word (freq 16,383),
+    one in which nearly every symbol does (freq 1: seven of eight) and seeded mixtures; bit bytes of 4, 5, 6 and 7 and some longer, so that the states and
+    words land on every byte alignment.  Symbols are well-formed: 1 <= freq, start + freq <= 2^14."""
+    rng = np.random.default_rng(corpus.SEED + 77)
+    frames = []
+    for n in (1, 2, 3, 4, 5, 7, 8, 255, 256, 257, 511, 512, 513, 1027):
+        for kind in ("none", "all", "mix", "mix2"):
+            if kind == "none":
+                freq = np.full(n, 16383, np.uint32)
+            elif kind == "all":
+                freq = np.ones(n, np.uint32)
+            else:
+                freq = rng.choice(np.array([1, 1, 2, 3, 100, 4096, 16383, 0], np.uint32), n)
+                rnd = rng.integers(1, 16384, n, dtype=np.uint32)
+                freq = np.where(freq == 0, rnd, freq).astype(np.uint32)
+            start = (rng.integers(0, 1 << 30, n, dtype=np.uint32) % (np.uint32(16385) - freq)).astype(np.uint32)
+            assert (freq >= 1).all() and (start + freq <= 1 << 14).all()
+            nb = 4 + len(frames) % 4 + (8 * int(rng.integers(0, 40)) if kind == "mix2" else 0)
+            frames.append(((start | (freq << np.uint32(16))).astype(np.uint32), rng.integers(0, 256, nb, dtype=np.uint8), int(rng.integers(0, 1 << 20))))
+    return frames
+
+
+def test_rans_frames_stage_many_sizes(gpu):
+    """rans_frames_kernel on 56 frames of different sizes in ONE call (so every frame but the longest lies short of the strides): each
+    frame byte for byte the oracle's CodeFrame::Flush, and the two extremes do what they are there for"""
+    frames = rans_stage_frames()
+    want = [oracle_py.flush_frame(s, b, o) for s, b, o in frames]
+    assert {len(b) % 4 for _, b, _ in frames} == {0, 1, 2, 3}
+    for (s, b, _), w, k in zip(frames, want, range(len(frames))):
+        if k % 4 == 0:
+            assert len(w) == 12 + len(b) + 16, "a frame in which no symbol pushes a word"
+        if k % 4 == 1:
+            assert len(w) >= 12 + len(b) + 16 + 2 * (max(0, len(s) - 4) * 3 // 4), "a frame in which nearly every symbol pushes a word"
+    got = gpu.rans_frames(frames)
+    bad = []
+    for k, (g, w) in enumerate(zip(got, want)):
+        if g != w:
+            i = next((i for i in range(min(len(g), len(w))) if g[i] != w[i]), min(len(g), len(w)))
+            where = f"{len(g)} bytes, want {len(w)}" if len(g) != len(w) else f"byte {i}: got 0x{g[i]:02X}, want 0x{w[i]:02X}"
+            bad.append(f"rans_frames_kernel: frame {k} ({len(frames[k][0])} symbols, {len(frames[k][1])} bit bytes): {where}")
+    assert not bad, "\n".join(bad[:20])
+
+
 def test_find_matches_stage(gpu):
     """Finder block of parse_table (NLZM.cpp:1501-1543): per-position match tables."""
     data = corpus.dups(200_000, corpus.SEED + 3)
