@@ -68,6 +68,7 @@ struct Counters {
     unsigned long long guess_used, guess_late, guess_wrong;   // rep-list waves: guessed rep set right / not seen in time / wrong
 };
 
+constexpr uint32_t kPfSlots = 128;      // Persist::prof
 // State that survives between launches (one per stream), in HBM.
 struct Persist {
     uint16_t cdf[kNumCtx * kCdfStride];
@@ -80,8 +81,108 @@ struct Persist {
     uint32_t error;             // 0 ok; see kErr*
     uint32_t error_info[3];
     Counters cnt;
-    unsigned long long prof[128];    // cycles per master phase (diagnostic builds: NLZM_PROFILE); 16..21: wait/total cycles per wave
+    unsigned long long prof[kPfSlots];   // the stages' accounting, summed over the launches: slot by slot below (ProfSlot)
 };
+
+// Persist::prof, slot by slot.  The numbers are fixed: profile logs and diagnostic builds keep their meaning.  Every stage adds its own
+// slots when it leaves a launch; "cycles" are xw::tick() differences (the simulation: scheduler sweeps); (profile) = counted by the
+// NLZM_PROFILE build only, zero otherwise.  A new counter takes a name here, a comment, and an entry in kProfSlots.
+enum ProfSlot : uint32_t {
+    kPfFinderBlocks = 0,        // finder: blocks evaluated
+    kPfFinderCutNice = 1,       // finder: blocks cut at a nice position
+    kPfFinderCutTop = 2,        // finder: blocks cut behind a new top entry
+    kPfFinderCutRkCand = 3,     // finder: blocks cut at an RK256 candidate
+    kPfFinderCutRkCatchUp = 4,  // finder: blocks cut by an RK256 catch-up
+    kPfFinderCutOther = 5,      // finder: blocks cut for any other reason
+    kPfTableBlocks = 6,         // table: blocks
+    kPfTableSlowBlocks = 7,     // table: blocks that took the serial path (a front beyond the launch's capacity)
+    kPfParserBlocks = 8,        // parser: blocks
+    kPfParserMaskFills = 9,     // parser: mask fills, carried in cnt.stale_ht (nothing raises the count at present: always 0)
+    kPfParserProbeRounds = 10,  // parser: rounds of the rep probes' compare loop, carried in cnt.stale_rk
+    kPfParserResampled = 11,    // parser: positions whose record was listed again (resample())
+    kPfFinderCutBin = 12,       // finder: blocks cut at a second position of the same worker bin
+    kPfParserPasses = 13,       // parser: passes, summed over the blocks
+    kPfParserResampledBack = 14,// parser: re-listings that put a record back as it was (read by the simulation's report only)
+    kPfFinderWait = 16,         // finder: cycles waiting (ring space, the parser's word, worker results)
+    kPfFinderTotal = 17,        // finder: cycles in the launch
+    kPfTableWait = 18,          // table: cycles wave 0 waited for its turn and for records
+    kPfTableTotal = 19,         // table: cycles of wave 0 in the launch
+    kPfParserWait = 20,         // parser: cycles waiting for records
+    kPfParserTotal = 21,        // parser: cycles in the launch
+    kPfParserEmit = 22,         // parser: cycles of backtrack and emission (wave 0)
+    kPfParserSetup = 23,        // parser: cycles of block set-up (wave 0)
+    kPfParserPass = 24,         // parser: cycles of the pass loops (wave 0)
+    kPfFinderWaitBt = 25,       // finder: the part of kPfFinderWait spent waiting for worker results
+    kPfParserNeed = 26,         // parser: times it waited for its record loader
+    kPfParserAhead = 27,        // parser: positions the table stage was ahead then, summed
+    kPfFinderLateUnc = 28,      // finder: worker results not there at the first look, positions whose call is the finder's decision
+    kPfFinderLateOther = 29,    // finder: the same, other positions
+    kPfParserWaveWork = 32,     // parser (profile): cycles of relax / probe work per pass loop, waves 0..3           [kPfParserWaveN]
+    kPfParserWaveBar = 36,      // parser (profile): cycles at the pass barrier, waves 0..3                           [kPfParserWaveN]
+    kPfParserUpdate = 40,       // parser (profile): cycles of wave 0's update
+    kPfParserFill = 41,         // parser (profile): cycles of mask fills (nothing raises it at present)
+    kPfParserBlockEnd = 42,     // parser (profile): cycles of wave 0 at a block's end
+    kPfParserDirty = 43,        // parser: cycles of "sets that changed" in the report; no build writes it
+    kPfTableGather = 44,        // table (profile): cycles gathering, summed over the waves
+    kPfTableScan = 45,          // table (profile): cycles of the scan
+    kPfTableMerge = 46,         // table (profile): cycles of the carry merge, the part in block order
+    kPfTableCarryWait = 47,     // table (profile): cycles waiting for the carry
+    kPfParserSec = 48,          // parser (profile): wave 0's cycles per pass loop by section -- relax, probe, clear; update: keys +
+                                //   cost scan, membership, winner sets, rest                                         [kPfParserSecN]
+    kPfTableRecords = 55,       // table (profile): cycles writing records
+    kPfParserLoaderSec = 56,    // parser (profile): the loader wave's cycles of block set-up by section -- block size + barrier,
+                                //   re-list, own edges, all edges, literal scan + clear + barrier                    [kPfParserLoaderSecN]
+    kPfParserAllWork = 64,      // parser (profile): cycles of work per pass loop, waves 0..7                         [kPfParserAllN]
+    kPfParserAllBar = 72,       // parser (profile): cycles at the pass barrier, waves 0..7                           [kPfParserAllN]
+    kPfParserAllUpdate = 80,    // parser (profile): cycles of the update, waves 0..7                                 [kPfParserAllN]
+    kPfFinderSec = 88,          // finder (profile): cycles of a block by section -- predict, own loads, HT rows, candidates + jobs,
+                                //   record + RK256, BT4 results (wait included), verify, commit                      [kPfFinderSecN]
+    kPfHelpJobs = 96,           // parser: jobs posted to the helper parsers
+    kPfHelpTaken = 97,          // parser: jobs whose nodes it took over
+    kPfHelpTakenNodes = 98,     // parser: nodes taken over
+    kPfHelpWait = 99,           // parser: cycles waiting for a helper (the simulation prints its sweeps)
+    kPfHelperJobs = 100,        // helpers: jobs seen
+    kPfHelperDone = 101,        // helpers: jobs done (every node up to the segment's end in the box)
+    kPfHelperBlocks = 102,      // helpers: blocks
+    kPfHelperPasses = 103,      // helpers: passes
+    kPfHelperWait = 104,        // helpers: cycles waiting for records
+    kPfTableFront = 105,        // table: blocks in which some front had more than 8 / 12 / 16 / 20 / 24 entries        [kPfTableFrontN]
+    kPfFinderLateHot = 110,     // finder: late worker results of hot bins' waves
+    kPfFinderLateFirst = 111,   // finder: late worker results at lane 0 (the position the block before was cut at)
+    kPfFinderLateBlocks = 112,  // finder: blocks that had to wait for a worker result
+    kPfTableShapeChanges = 113, // table: launches that left another shape for the next
+    kPfTableWideLaunches = 114, // table: launches in the wide shape
+    kPfRkShortTop = 115,        // finder: cut-short RK256 entries that became the growing top entry
+    kPfRkShortTie = 116,        // finder: ... that ended exactly where another entry ends
+    kPfRkShortWon = 117,        // finder: ... and were the nearer one of the two
+    kPfFinderSegOwn = 118,      // finder: starts of nice regions whose segment the stage knew itself
+    kPfFinderSegWait = 119,     // finder: ... that it had to wait for the parser's word for
+};
+constexpr uint32_t kPfParserWaveN = 4, kPfParserSecN = 7, kPfParserLoaderSecN = 5, kPfParserAllN = 8, kPfFinderSecN = 8, kPfTableFrontN = 5;
+// every named slot, {first, width}: no two may overlap (a new counter on a used slot does not compile)
+struct ProfRun { uint32_t first, width; };
+constexpr ProfRun kProfSlots[] = {
+    { kPfFinderBlocks, 1 }, { kPfFinderCutNice, 1 }, { kPfFinderCutTop, 1 }, { kPfFinderCutRkCand, 1 }, { kPfFinderCutRkCatchUp, 1 }, { kPfFinderCutOther, 1 },
+    { kPfTableBlocks, 1 }, { kPfTableSlowBlocks, 1 }, { kPfParserBlocks, 1 }, { kPfParserMaskFills, 1 }, { kPfParserProbeRounds, 1 }, { kPfParserResampled, 1 },
+    { kPfFinderCutBin, 1 }, { kPfParserPasses, 1 }, { kPfParserResampledBack, 1 }, { kPfFinderWait, 1 }, { kPfFinderTotal, 1 }, { kPfTableWait, 1 }, { kPfTableTotal, 1 },
+    { kPfParserWait, 1 }, { kPfParserTotal, 1 }, { kPfParserEmit, 1 }, { kPfParserSetup, 1 }, { kPfParserPass, 1 }, { kPfFinderWaitBt, 1 }, { kPfParserNeed, 1 },
+    { kPfParserAhead, 1 }, { kPfFinderLateUnc, 1 }, { kPfFinderLateOther, 1 }, { kPfParserWaveWork, kPfParserWaveN }, { kPfParserWaveBar, kPfParserWaveN },
+    { kPfParserUpdate, 1 }, { kPfParserFill, 1 }, { kPfParserBlockEnd, 1 }, { kPfParserDirty, 1 }, { kPfTableGather, 1 }, { kPfTableScan, 1 }, { kPfTableMerge, 1 },
+    { kPfTableCarryWait, 1 }, { kPfParserSec, kPfParserSecN }, { kPfTableRecords, 1 }, { kPfParserLoaderSec, kPfParserLoaderSecN }, { kPfParserAllWork, kPfParserAllN },
+    { kPfParserAllBar, kPfParserAllN }, { kPfParserAllUpdate, kPfParserAllN }, { kPfFinderSec, kPfFinderSecN }, { kPfHelpJobs, 1 }, { kPfHelpTaken, 1 },
+    { kPfHelpTakenNodes, 1 }, { kPfHelpWait, 1 }, { kPfHelperJobs, 1 }, { kPfHelperDone, 1 }, { kPfHelperBlocks, 1 }, { kPfHelperPasses, 1 }, { kPfHelperWait, 1 },
+    { kPfTableFront, kPfTableFrontN }, { kPfFinderLateHot, 1 }, { kPfFinderLateFirst, 1 }, { kPfFinderLateBlocks, 1 }, { kPfTableShapeChanges, 1 },
+    { kPfTableWideLaunches, 1 }, { kPfRkShortTop, 1 }, { kPfRkShortTie, 1 }, { kPfRkShortWon, 1 }, { kPfFinderSegOwn, 1 }, { kPfFinderSegWait, 1 },
+};
+constexpr bool prof_slots_disjoint()
+{
+    for (const ProfRun &a : kProfSlots) {
+        if (!a.width || a.first + a.width > kPfSlots) return false;
+        for (const ProfRun &b : kProfSlots) if (&a != &b && a.first < b.first + b.width && b.first < a.first + a.width) return false;
+    }
+    return true;
+}
+static_assert(prof_slots_disjoint(), "two names of Persist::prof share a slot, or one lies beyond the array");
 
 constexpr uint32_t kErrFrameOverflow = 1;
 constexpr uint32_t kErrTimeout = 2;
@@ -133,6 +234,7 @@ constexpr uint32_t kBtRec = 16;         // words per bt_ready record
 NLZM_HD uint32_t bt_rec_d(uint32_t k) { return k == 0 ? 4u : (k == 1 ? 6u : (k == 2 ? 9u : 12u)); }
 NLZM_HD uint32_t bt_rec_l(uint32_t k) { return k == 0 ? 5u : (k == 1 ? 8u : (k == 2 ? 10u : 13u)); }
 
+constexpr uint32_t kHcCols = 21;        // WorkerCounters::hot_class
 struct WorkerCounters {
     unsigned long long bt_calls, bt_tests, cmp_bytes, dry_runs, flag_waits;
     unsigned long long call_cycles, call_tests;     // diagnostics: cycles / tests of the write-mode calls (per-lane clocks)
@@ -140,17 +242,32 @@ struct WorkerCounters {
     unsigned long long hot_bins, hot_calls;         // hot bins over all launches; calls made by their waves
     unsigned long long spec_calls, spec_good;       // decisions "skip" that took calls back; calls behind the skipped position that were made again
     unsigned long long hot_steps, hot_blocked_dry, hot_blocked_risky;   // hot bins' waves: steps; steps in which the next call could not start (a call without stores on its way / a risky assumption open)
-    // hot bins' waves by the size of the bin (class k: 8,192 << k positions of the launch and more; the last class is open), what their steps were spent on:
-    //   0 waves, 1 calls, 2 tests, 3 steps, 4 steps in which some lane made a test, 5 tests made (summed over the lanes), 6 lane-steps repeated for a slot
-    //   another call holds, 7 idle steps while a wrong assumption is taken back, 8 idle: every lane holds a call that waits for a decision, 9 idle: the next
-    //   call may not start (dry / risky), 10 idle: no entry (the chunk's end, or its calls are held), 11 cycles, 12 entries skipped (decided "skip" when they came up),
-    //   13 idle steps with an undecided position open (any cause)
-    //   (4 .. 10 and 13 are counted by the profile build only, NLZM_PROFILE: counting them was a tenth of a step)
-    //   14 .. 20 (profile build): cycles of a step by section -- the oldest undecided position and recovery, passing entries and the start, the step's loads
-    //   until they are back (the round trip), a call's start and its test, the call's end and its result, accounting and watchdogs; 20: the end of the step before
-    //   and the windows' upkeep (in front of 14)
-    unsigned long long hot_class[8][21];
+    // hot bins' waves by the size of the bin (class k: 8,192 << k positions of the launch and more; the last class is open), what their steps were spent
+    // on: column by column below (HotCol)
+    unsigned long long hot_class[8][kHcCols];
 };
+// WorkerCounters::hot_class, column by column.  (profile) = counted by the NLZM_PROFILE build only: counting them was a tenth of a step.
+enum HotCol : uint32_t {
+    kHcWaves = 0,           // waves
+    kHcCalls = 1,           // calls
+    kHcTests = 2,           // tests
+    kHcSteps = 3,           // steps
+    kHcTestSteps = 4,       // (profile) steps in which some lane made a test
+    kHcLaneTests = 5,       // (profile) tests made, summed over the lanes
+    kHcRepeats = 6,         // (profile) lane-steps repeated for a slot another call holds
+    kHcTakingBack = 7,      // (profile) idle steps while a wrong assumption is taken back
+    kHcAllHold = 8,         // (profile) idle steps: every lane holds a call that waits for a decision
+    kHcMayNotStart = 9,     // (profile) idle steps: the next call may not start (dry / risky)
+    kHcNoEntry = 10,        // (profile) idle steps: no entry (the chunk's end, or its calls are held)
+    kHcCycles = 11,         // cycles
+    kHcSkipped = 12,        // entries skipped (decided "skip" when they came up)
+    kHcIdleUndecided = 13,  // (profile) idle steps with an undecided position open (any cause)
+    kHcSec = 14,            // (profile) cycles of a step by section -- the oldest undecided position and recovery, passing entries and the start, the step's
+                            //   loads until they are back (the round trip), a call's start and its test, the call's end and its result, accounting and
+                            //   watchdogs, the end of the step before and the windows' upkeep (in front of the first)      [kHcSecN]
+};
+constexpr uint32_t kHcSecN = 7;
+static_assert(kHcSec + kHcSecN == kHcCols, "WorkerCounters::hot_class");
 
 // Everything the master needs from HBM.
 struct Globals {

@@ -25,6 +25,7 @@
 #include "../../include/nlzm_hip.h"
 #include "nlzm_core.h"
 #include "nlzm_v2.h"
+#include "nlzm_report.h"
 
 #include "nlzm_launch.h"
 
@@ -158,11 +159,14 @@ struct StreamBuffers {
     v2::HelpBox *v2_hb = nullptr;
 };
 
+// the events of a launch set: what a step brackets with them, and two for a call's own timing (nlzm_hip_compress: upload and download; a block set's step: its device time)
+enum { kEvLaunchBegin, kEvLaunchEnd /* = frame coder begin */, kEvCoderEnd, kEvGatherBegin, kEvGatherEnd, kEvRkBegin, kEvRkEnd /* = rest of the pre-pass begin */, kEvPrepEnd,
+       kEvCallBegin, kEvCallEnd, kEvN };
 struct Ctx {
     bool inited = false;
     int device = 0, cu_count = 0;
     hipStream_t st = nullptr;
-    hipEvent_t ev[2][8] = {};               // per launch set (the second one's: block mode)
+    hipEvent_t ev[2][kEvN] = {};             // per launch set (the second one's: block mode)
     Pool *pool = nullptr;                   // (block mode) where the stream's buffers come from
 
     // the open stream
@@ -201,9 +205,9 @@ struct Ctx {
     nlzm_hip_stats stats{};
     nlzm_hip_timing tm{};
     // of the last finished stream
-    unsigned long long prof_last[128] = {}; // Persist::prof and the worker lanes' counters (nlzm_hip_get_counter)
+    unsigned long long prof_last[kPfSlots] = {}; // Persist::prof and the worker lanes' counters (nlzm_hip_get_counter)
     WorkerCounters wc_last{};
-    double acct[8] = {};                    // cycles per position: finder total / wait / of it for BT4, table total / wait, parser total / wait / passes
+    double acct[8] = {};                    // cycles per position, row by row of kAcctRows (nlzm_report.h)
 };
 
 // a device buffer of the stream: from its pool, or from hipMalloc (then the stream owns it)
@@ -560,12 +564,12 @@ int step_pre(Ctx &C, uint32_t todo, StepPlan &P, bool ahead = false)
         const unsigned long long lo = a0 > 1024 ? a0 - 1024 : 0;
         unsigned long long hi = a1 + g.feed + 256;
         if (hi + 255 > g.n) hi = g.n >= 255 ? g.n - 255 : 0;
-        HIPCHK(hipEventRecord(ev[7], C.st));
+        HIPCHK(hipEventRecord(ev[kEvRkBegin], C.st));
         if (hi > lo && hi - lo > K.rkhash_len) return set_err(NLZM_HIP_E_ARG, "launch of %u chunks is larger than the stream was opened for", nb);
         G.rkhash = L.rkhash - lo;                       // rkhash[a] for a in [lo, hi): the launch's own array
         if (g.n >= 256 && hi > lo) launch_rk_hash(C.d_in, g.n, lo, hi, L.rkhash - lo, C.st);
     }
-    HIPCHK(hipEventRecord(ev[5], C.st));
+    HIPCHK(hipEventRecord(ev[kEvRkEnd], C.st));
     {
         const unsigned long long cnt = a1 - a0;
         G.bt_ready = L.bt_ready; G.bt_pairs = B.bt_pairs; G.bt_flag = L.bt_flag; G.unc = L.unc;
@@ -599,7 +603,7 @@ int step_pre(Ctx &C, uint32_t todo, StepPlan &P, bool ahead = false)
         G.test_fail = K.test_fail_launch >= 0 && (int64_t)C.v2_launch_no == K.test_fail_launch ? 1u : 0u;
         G.table_shape = K.table_shape; G.launch_par = (uint32_t)(C.v2_launch_no++ & 1u);
     }
-    HIPCHK(hipEventRecord(ev[6], C.st));
+    HIPCHK(hipEventRecord(ev[kEvPrepEnd], C.st));
     return 0;
 }
 
@@ -614,10 +618,10 @@ int step_post_issue(Ctx &C, const StepPlan &P)
     const uint32_t nb = P.nb;
     C.post_hm.resize(nb); C.post_hoff.resize(nb);
     C.post_aborted = 0;
-    HIPCHK(hipEventRecord(ev[1], C.st));
+    HIPCHK(hipEventRecord(ev[kEvLaunchEnd], C.st));
     launch_rans(L.syms, K.syms_stride, L.bits, K.bits_stride, L.fmeta, C.buf.scratch, K.syms_stride, C.buf.frames,
                 K.frame_stride, (uint32_t)K.frame_stride, nb, C.st);
-    HIPCHK(hipEventRecord(ev[2], C.st));
+    HIPCHK(hipEventRecord(ev[kEvCoderEnd], C.st));
     HIPCHK(hipMemcpyAsync(C.post_hm.data(), L.fmeta, nb * sizeof(FrameMeta), hipMemcpyDeviceToHost, C.st));
     if (P.ahead) {          // (the stream's next launch may be running: the copy round_close_kernel made)
         HIPCHK(hipMemcpyAsync(&C.post_snap, L.snap, sizeof(v2::RoundSnap), hipMemcpyDeviceToHost, C.st));
@@ -643,8 +647,8 @@ int step_post_check(Ctx &C, const StepPlan &P)
     const Persist &Pst = C.post_P;
     const uint32_t aborted = C.post_aborted;
     float rk_ms = 0, pre_ms = 0;
-    HIPCHK(hipEventElapsedTime(&rk_ms, ev[7], ev[5]));
-    HIPCHK(hipEventElapsedTime(&pre_ms, ev[5], ev[6]));
+    HIPCHK(hipEventElapsedTime(&rk_ms, ev[kEvRkBegin], ev[kEvRkEnd]));
+    HIPCHK(hipEventElapsedTime(&pre_ms, ev[kEvRkEnd], ev[kEvPrepEnd]));
     C.tm.prep_ms += rk_ms + pre_ms; C.tm.prep_launches += 5; C.tm.total_ms += rk_ms + pre_ms;
     C.arena_out = false;
     if (Pst.error || C.hx_host.err) {
@@ -652,19 +656,9 @@ int step_post_check(Ctx &C, const StepPlan &P)
         const v2::Hx &h = C.hx_host;
         WorkerCounters wc{};
         (void)hipMemcpy(&wc, C.buf.wcnt, sizeof wc, hipMemcpyDeviceToHost);
-        return set_err(NLZM_HIP_E_KERNEL,
-                       "device error %u in chunks [%u,%u) (parser stopped at chunk %u): raised by stage %u at wait site %u, position %u, saw %u %u | "
-                       "progress: finder %u, table in %u out %u, parser %u, segment %u covered to %u | "
-                       "finder: block at %u reach %u top entry %u d %u end %u prev_nice %u seg_s %u rk_len %u t_pos_seen %u err %u base %u | "
-                       "table: cursor %u turn %u carry_seq %u f_seen %u p_seen %u carry_n %u | "
-                       "parser: chunk %u segment %u block node %u max_parse %u staged to %u t_out_seen %u err %u | "
-                       "worker lanes left waiting %llu, first of them at position %u",
-                       Pst.error ? Pst.error : h.err, c0, c1, Pst.next_chunk, h.err_info[0], h.err_info[1], h.err_info[2], h.err_info[3], h.err_info[4],
-                       h.f_pos, h.t_pos, h.t_out, h.p_pos, (uint32_t)(h.p_seg >> 32), (uint32_t)h.p_seg,
-                       h.dbg[0][0], h.dbg[0][1], h.dbg[0][2], h.dbg[0][3], h.dbg[0][4], h.dbg[0][5], h.dbg[0][6], h.dbg[0][7], h.dbg[0][8], h.dbg[0][9], h.dbg[0][10],
-                       h.dbg[1][0], h.dbg[1][1], h.dbg[1][2], h.dbg[1][3], h.dbg[1][4], h.dbg[1][5],
-                       h.dbg[2][0], h.dbg[2][1], h.dbg[2][2], h.dbg[2][3], h.dbg[2][4], h.dbg[2][5], h.dbg[2][6],
-                       wc.stuck_lanes, wc.stuck_lanes ? (uint32_t)~(uint32_t)wc.stuck_pos_inv : 0u);
+        char where[sizeof g_err];
+        stage_error_text(where, sizeof where, h, wc);
+        return set_err(NLZM_HIP_E_KERNEL, "device error %u in chunks [%u,%u) (parser stopped at chunk %u): %s", Pst.error ? Pst.error : h.err, c0, c1, Pst.next_chunk, where);
     }
     // (the worker lanes drop a pair that finds no extension block and go on: the cursor says how many blocks were asked for)
     C.arena_out = K.ext_cap && C.hx_host.ext_cur > K.ext_cap;
@@ -690,9 +684,9 @@ int step_post_check(Ctx &C, const StepPlan &P)
         C.got = true;
     }
     HIPCHK(hipMemcpyAsync(C.buf.dst_off, hoff.data(), nb * sizeof(unsigned long long), hipMemcpyHostToDevice, C.st));
-    HIPCHK(hipEventRecord(ev[3], C.st));
+    HIPCHK(hipEventRecord(ev[kEvGatherBegin], C.st));
     launch_gather(C.buf.frames, K.frame_stride, C.buf.dst_off, L.fmeta, C.d_dst, nb, C.st);
-    HIPCHK(hipEventRecord(ev[4], C.st));
+    HIPCHK(hipEventRecord(ev[kEvGatherEnd], C.st));
     C.post_pos = pos;
     return 0;
 }
@@ -703,9 +697,9 @@ int step_post_done(Ctx &C, const StepPlan &P, float pipe_ms)
     const uint32_t c1 = P.c1;
     HIPCHK(hipStreamSynchronize(C.st));
     float a = pipe_ms, b = 0, c = 0;
-    if (pipe_ms < 0) HIPCHK(hipEventElapsedTime(&a, ev[0], ev[1]));
-    HIPCHK(hipEventElapsedTime(&b, ev[1], ev[2]));
-    HIPCHK(hipEventElapsedTime(&c, ev[3], ev[4]));
+    if (pipe_ms < 0) HIPCHK(hipEventElapsedTime(&a, ev[kEvLaunchBegin], ev[kEvLaunchEnd]));
+    HIPCHK(hipEventElapsedTime(&b, ev[kEvLaunchEnd], ev[kEvCoderEnd]));
+    HIPCHK(hipEventElapsedTime(&c, ev[kEvGatherBegin], ev[kEvGatherEnd]));
     C.tm.match_parse_ms += a; C.tm.match_parse_launches++;
     if (a > 0) C.last_launch_ms = a;
     C.tm.rans_ms += b + c; C.tm.rans_launches++;
@@ -732,7 +726,7 @@ int stream_step(Ctx &C, uint32_t max_chunks, uint64_t *in_done, uint64_t *out_do
         StepPlan P;
         int rc = step_pre(C, todo, P);
         if (rc) return rc;
-        HIPCHK(hipEventRecord(C.ev[P.set][0], C.st));
+        HIPCHK(hipEventRecord(C.ev[P.set][kEvLaunchBegin], C.st));
         launch_pipeline2(g, P.G, P.V, P.c0, P.c1, C.cfg.worker_blocks, C.st);
         rc = step_post(C, P, -1.0f);
         if (rc) return rc;
@@ -745,89 +739,6 @@ int stream_step(Ctx &C, uint32_t max_chunks, uint64_t *in_done, uint64_t *out_do
     if (out_done) *out_done = C.out_pos;
     if (finished) *finished = C.next_chunk >= g.nchunks;
     return 0;
-}
-
-// per-stage accounting of the three-stage pipeline (Persist::prof, filled by nlzm_v2.h) on stderr: option "stage_report"
-void stage_report(const Persist &P)
-{
-    const double n = (double)(P.cnt.positions ? P.cnt.positions : 1);
-    fprintf(stderr, "cycles/position  finder: total %.0f wait %.0f (%.0f of it for worker results) | table: total %.0f wait %.0f | parser: total %.0f wait %.0f (block set-up %.0f, passes %.0f, emit %.0f)\n",
-            P.prof[17] / n, P.prof[16] / n, P.prof[25] / n, P.prof[19] / n, P.prof[18] / n, P.prof[21] / n, P.prof[20] / n, P.prof[23] / n, P.prof[24] / n, P.prof[22] / n);
-    fprintf(stderr, "finder: %llu blocks (%.1f positions each); cut by: nice %llu, new top entry %llu, RK candidate %llu, RK catch-up %llu, same worker bin %llu, other %llu\n",
-            P.prof[0], n / (double)(P.prof[0] ? P.prof[0] : 1), P.prof[1], P.prof[2], P.prof[3], P.prof[4], P.prof[12], P.prof[5]);
-    fprintf(stderr, "table: %llu blocks, %llu on the slow path; parser: %llu blocks (%.1f nodes each), %.2f passes per block (%.0f cycles per pass), mask fills %llu, probe rounds %llu, re-sampled %llu\n",
-            P.prof[6], P.prof[7], P.prof[8], n / (double)(P.prof[8] ? P.prof[8] : 1), (double)P.prof[13] / (double)(P.prof[8] ? P.prof[8] : 1),
-            (double)P.prof[24] / (double)(P.prof[13] ? P.prof[13] : 1), P.prof[9], P.prof[10], P.prof[11]);
-    fprintf(stderr, "table: %llu launches with %u-entry fronts on %u waves (the others: %u on %u), the shape changed %llu times\n", P.prof[114], v2::kFrCapWide, v2::kTWWide, v2::kFrCap, v2::kTW, P.prof[113]);
-    fprintf(stderr, "table: blocks in which some position's front had more than 8 / 12 / 16 / 20 / 24 / the launch's capacity of entries at some step of the scan: %.2f / %.2f / %.2f / %.3f / %.3f / %.3f %%\n",
-            100.0 * P.prof[105] / (P.prof[6] ? P.prof[6] : 1), 100.0 * P.prof[106] / (P.prof[6] ? P.prof[6] : 1), 100.0 * P.prof[107] / (P.prof[6] ? P.prof[6] : 1),
-            100.0 * P.prof[108] / (P.prof[6] ? P.prof[6] : 1), 100.0 * P.prof[109] / (P.prof[6] ? P.prof[6] : 1), 100.0 * P.prof[7] / (P.prof[6] ? P.prof[6] : 1));
-    fprintf(stderr, "finder: RK256 entries cut short by the uint16 length parameter that became the growing top entry: %llu; that ended exactly where another entry ends: %llu (%llu of them the nearer one)\n",
-            P.prof[115], P.prof[116], P.prof[117]);
-    fprintf(stderr, "finder: starts of nice regions whose segment the stage knew itself, ahead of the parser's word: %llu; that it had to wait for: %llu\n", P.prof[118], P.prof[119]);
-    fprintf(stderr, "finder: worker results not there at the first look: %llu of positions whose call is the finder's decision (unc), %llu of others\n", P.prof[28], P.prof[29]);
-    fprintf(stderr, "finder: blocks that had to wait for a worker result: %llu (%.0f cycles each); late results of hot bins' waves %llu, late results at lane 0 (the position the block before was cut at) %llu\n",
-            P.prof[112], (double)P.prof[25] / (double)(P.prof[112] ? P.prof[112] : 1), P.prof[110], P.prof[111]);
-    fprintf(stderr, "parser: waited for its record loader %llu times, the table stage %.0f positions ahead on average then\n", P.prof[26], (double)P.prof[27] / (double)(P.prof[26] ? P.prof[26] : 1));
-    if (P.prof[96] || P.prof[100])
-        fprintf(stderr, "helper parser: %llu jobs posted, %llu taken over (%llu nodes = %.1f %% of the positions), the parser stage waited %.0f cycles per position for it; "
-                        "helper: %llu jobs seen, %llu done, %llu blocks (%.2f passes each), waited %.0f cycles per position for records\n",
-                P.prof[96], P.prof[97], P.prof[98], 100.0 * P.prof[98] / n, P.prof[99] / n, P.prof[100], P.prof[101], P.prof[102],
-                (double)P.prof[103] / (double)(P.prof[102] ? P.prof[102] : 1), P.prof[104] / n);
-    if (P.prof[88]) fprintf(stderr, "finder sections (cycles/position, profile build): predict %.0f, own loads %.0f, HT rows %.0f, candidates + jobs %.0f, record + RK256 %.0f, "
-                            "BT4 results (wait included) %.0f, verify %.0f, commit %.0f\n", P.prof[88] / n, P.prof[89] / n, P.prof[90] / n, P.prof[91] / n, P.prof[92] / n,
-                            P.prof[93] / n, P.prof[94] / n, P.prof[95] / n);
-    if (P.prof[44]) fprintf(stderr, "table stage sections (cycles/position summed over the waves, profile build): gather %.0f, scan %.0f, waiting for the carry %.0f, carry merge (the part in block order) %.0f, records %.0f\n",
-                            P.prof[44] / n, P.prof[45] / n, P.prof[47] / n, P.prof[46] / n, P.prof[55] / n);
-    if (P.prof[32]) {
-        const double np = (double)(P.prof[13] ? P.prof[13] : 1);
-        fprintf(stderr, "parser, cycles per pass (profile build): relax waves %.0f %.0f %.0f, probe wave %.0f (of it: sets that changed %.0f, mask fills %.0f), update %.0f, "
-                        "barrier waits per wave %.0f %.0f %.0f %.0f; block end %.0f cycles/position\n",
-                P.prof[32] / np, P.prof[33] / np, P.prof[34] / np, P.prof[35] / np, P.prof[43] / np, P.prof[41] / np, P.prof[40] / np,
-                P.prof[36] / np, P.prof[37] / np, P.prof[38] / np, P.prof[39] / np, P.prof[42] / n);
-        fprintf(stderr, "parser, cycles per pass by wave 0..7 (profile build): work");
-        for (int w = 0; w < 8; w++) fprintf(stderr, " %.0f", P.prof[64 + w] / np);
-        fprintf(stderr, " | barrier wait");
-        for (int w = 0; w < 8; w++) fprintf(stderr, " %.0f", P.prof[72 + w] / np);
-        fprintf(stderr, " | update");
-        for (int w = 0; w < 8; w++) fprintf(stderr, " %.0f", P.prof[80 + w] / np);
-        fprintf(stderr, "\n");
-        const double nbk = (double)(P.prof[8] ? P.prof[8] : 1);
-        fprintf(stderr, "parser loader wave, cycles per block set-up: block size + barrier %.0f, re-list %.0f, own edges %.0f, all edges %.0f, literal scan + clear + barrier %.0f\n",
-                P.prof[56] / nbk, P.prof[57] / nbk, P.prof[58] / nbk, P.prof[59] / nbk, P.prof[60] / nbk);
-        fprintf(stderr, "parser wave 0, cycles per pass: relax %.0f, probe %.0f, clear %.0f | update: keys + cost scan %.0f, membership %.0f, winner sets %.0f, rest %.0f\n",
-                P.prof[48] / np, P.prof[49] / np, P.prof[50] / np, P.prof[51] / np, P.prof[52] / np, P.prof[53] / np, P.prof[54] / np);
-    }
-}
-// ... and of the worker lanes
-void worker_report(const WorkerCounters &wc, bool hot)
-{
-    fprintf(stderr, "worker lanes: %llu calls made with their fate open (at and behind a position not decided yet), %llu decisions that took calls back, %llu calls made again for it\n",
-            wc.dry_runs, wc.spec_calls, wc.spec_good);
-    if (hot)
-        fprintf(stderr, "hot bins (a wave each): %llu over all launches, %llu of %llu calls made by their waves\n", wc.hot_bins, wc.hot_calls, wc.bt_calls);
-    if (hot && wc.hot_steps) {
-            fprintf(stderr, "hot bins' waves: %llu steps (%.1f per call); the next call could not start in %.1f %% of them (a call without its stores on its way) + %.1f %% (an assumed \"skip\" behind a \"call\" still open); lanes: %llu turns spent waiting for a decision\n",
-                    wc.hot_steps, (double)wc.hot_steps / (wc.hot_calls ? wc.hot_calls : 1), 100.0 * wc.hot_blocked_dry / wc.hot_steps, 100.0 * wc.hot_blocked_risky / wc.hot_steps, wc.flag_waits);
-        // (what a step was spent on is counted by the profile build only: the counting was a tenth of the step)
-        fprintf(stderr, "hot bins' waves by the bin's positions in the launch (class: waves | calls, tests/call, entries skipped | steps, cycles/step; the profile build adds | %% of the steps: some lane tests "
-                        "(tests per such step; lane-steps repeated for a held slot per step), taking back, every lane holds a call, next call may not start, no entry | idle steps with an undecided position open)\n");
-        for (int k = 0; k < 8; k++) {
-            const unsigned long long *h = wc.hot_class[k];
-            if (!h[0]) continue;
-            const double st = (double)(h[3] ? h[3] : 1);
-            fprintf(stderr, "  %s %7u: %5llu | %10llu calls, %5.1f, %10llu | %12llu steps, %5.0f", k ? ">=" : "< ", k ? 8192u << k : 16384u, h[0], h[1], (double)h[2] / (h[1] ? h[1] : 1), h[12], h[3], (double)h[11] / st);
-            if (h[14] + h[16]) {
-                fprintf(stderr, " | %4.1f (%.2f; %.2f), %4.1f, %4.1f, %4.1f, %4.1f | %4.1f\n", 100.0 * h[4] / st, (double)h[5] / (h[4] ? h[4] : 1), (double)h[6] / st, 100.0 * h[7] / st, 100.0 * h[8] / st, 100.0 * h[9] / st,
-                        100.0 * h[10] / st, 100.0 * h[13] / st);
-                fprintf(stderr, "              cycles of a step by section: end of the step before + windows %.0f, oldest undecided + recovery %.0f, entries passed + start %.0f, loads until they are back %.0f, "
-                                "call start / test %.0f, call end + result %.0f, accounting + watchdogs %.0f\n", h[20] / st, h[14] / st, h[15] / st, h[16] / st, h[17] / st, h[18] / st, h[19] / st);
-            } else fprintf(stderr, "\n");
-        }
-    }
-    if (wc.call_tests)
-        fprintf(stderr, "worker lanes: %.0f cycles per BT4 test, %.1f tests per timed call (lane clocks, divergence included)\n",
-                (double)wc.call_cycles / wc.call_tests, (double)wc.call_tests / (wc.bt_calls ? wc.bt_calls : 1));
 }
 
 // report: the stages' cycle accounting of the stream on stderr (option "stage_report")
@@ -843,17 +754,13 @@ int refresh_stats(Ctx &C, bool report)
     s.n_dict = P.cnt.n_dict; s.n_rep = P.cnt.n_rep; s.rans_syms = P.cnt.rans_syms; s.bit_ops = P.cnt.bit_ops;
     s.frames = P.cnt.frames; s.shifts = P.cnt.shifts; s.uncertain_positions = P.cnt.uncertain_positions;
     memcpy(C.prof_last, P.prof, sizeof C.prof_last);
-    {
-        const double n = (double)(P.cnt.positions ? P.cnt.positions : 1);
-        C.acct[0] = P.prof[17] / n; C.acct[1] = P.prof[16] / n; C.acct[2] = P.prof[25] / n; C.acct[3] = P.prof[19] / n; C.acct[4] = P.prof[18] / n;
-        C.acct[5] = P.prof[21] / n; C.acct[6] = P.prof[20] / n; C.acct[7] = P.prof[24] / n;
-    }
-    if (report) stage_report(P);
+    acct_figures(P, C.acct);
+    if (report) stage_report(stderr, P);
     WorkerCounters wc;
     HIPCHK(hipMemcpy(&wc, C.buf.wcnt, sizeof wc, hipMemcpyDeviceToHost));
     s.bt_calls += wc.bt_calls; s.bt_tests += wc.bt_tests; s.cmp_bytes += wc.cmp_bytes;
     C.wc_last = wc;
-    if (report) worker_report(wc, C.cfg.hot_max != 0);
+    if (report) worker_report(stderr, wc, C.cfg.hot_max != 0);
     return 0;
 }
 
@@ -1006,12 +913,12 @@ int nlzm_hip_compress(const uint8_t *src, uint64_t n, uint32_t hist_bits_req, ui
     const uint64_t bound = nlzm_hip_compress_bound(n);
     int rc = alloc_own_io(C, n, bound);
     if (rc) return rc;
-    HIPCHK(hipEventRecord(C.ev[0][5], C.st));
+    HIPCHK(hipEventRecord(C.ev[0][kEvCallBegin], C.st));
     if (n) HIPCHK(hipMemcpyAsync(C.own_in, src, n, hipMemcpyHostToDevice, C.st));
-    HIPCHK(hipEventRecord(C.ev[0][6], C.st));
+    HIPCHK(hipEventRecord(C.ev[0][kEvCallEnd], C.st));
     HIPCHK(hipStreamSynchronize(C.st));
     float h2d = 0;
-    HIPCHK(hipEventElapsedTime(&h2d, C.ev[0][5], C.ev[0][6]));
+    HIPCHK(hipEventElapsedTime(&h2d, C.ev[0][kEvCallBegin], C.ev[0][kEvCallEnd]));
     rc = stream_begin(C, D.opt, C.own_in, n, hist_bits_req, C.own_dst, bound);
     if (rc) return rc;
     rc = stream_step(C, 0, nullptr, nullptr, nullptr);
@@ -1020,12 +927,12 @@ int nlzm_hip_compress(const uint8_t *src, uint64_t n, uint32_t hist_bits_req, ui
     rc = stream_finish(C, &len, D.opt.report != 0);
     if (rc) return rc;
     if (len > dst_cap) return set_err(NLZM_HIP_E_CAPACITY, "stream is %llu bytes, dst_cap %llu", (unsigned long long)len, (unsigned long long)dst_cap);
-    HIPCHK(hipEventRecord(C.ev[0][5], C.st));
+    HIPCHK(hipEventRecord(C.ev[0][kEvCallBegin], C.st));
     HIPCHK(hipMemcpyAsync(dst, C.own_dst, len, hipMemcpyDeviceToHost, C.st));
-    HIPCHK(hipEventRecord(C.ev[0][6], C.st));
+    HIPCHK(hipEventRecord(C.ev[0][kEvCallEnd], C.st));
     HIPCHK(hipStreamSynchronize(C.st));
     float d2h = 0;
-    HIPCHK(hipEventElapsedTime(&d2h, C.ev[0][5], C.ev[0][6]));
+    HIPCHK(hipEventElapsedTime(&d2h, C.ev[0][kEvCallBegin], C.ev[0][kEvCallEnd]));
     C.tm.h2d_ms = h2d; C.tm.d2h_ms = d2h;
     *dst_len = len;
     return 0;
@@ -1050,19 +957,7 @@ int nlzm_hip_get_counter(const char *key, uint64_t *value)
     if (!strncmp(key, "crc_", 4)) return nlzm::crc_counter(key, value);
     if (!strncmp(key, "range_", 6)) return nlzm::range_counter(key, value);
     if (C.open) { const int rc = refresh_stats(C, D.opt.report != 0); if (rc) return rc; }
-    static const struct { const char *name; int idx; } kProf[] = {
-        { "finder_blocks", 0 }, { "table_blocks", 6 }, { "parser_blocks", 8 }, { "parser_passes", 13 },
-        { "finder_wait_cycles", 16 }, { "finder_total_cycles", 17 }, { "table_wait_cycles", 18 }, { "table_total_cycles", 19 },
-        { "parser_wait_cycles", 20 }, { "parser_total_cycles", 21 }, { "parser_emit_cycles", 22 }, { "parser_setup_cycles", 23 }, { "parser_pass_cycles", 24 },
-        { "finder_bt_wait_cycles", 25 }, { "table_slow_blocks", 7 }, { "rk_cut_short_grown", 115 }, { "rk_cut_short_ties", 116 }, { "rk_cut_short_ties_won", 117 }, { "table_shape_changes", 113 }, { "table_wide_launches", 114 },
-        { "finder_seg_own", 118 }, { "finder_seg_waited", 119 }, { "helper_jobs", 96 }, { "helper_taken", 97 }, { "helper_taken_nodes", 98 }, { "helper_wait_cycles", 99 }, { "helper_jobs_done", 101 }, { "helper_blocks", 102 }, { "helper_passes", 103 },
-    };
-    for (const auto &e : kProf) if (!strcmp(key, e.name)) { *value = C.prof_last[e.idx]; return 0; }
-    if (!strcmp(key, "worker_call_cycles")) { *value = C.wc_last.call_cycles; return 0; }
-    if (!strcmp(key, "worker_call_tests")) { *value = C.wc_last.call_tests; return 0; }
-    if (!strcmp(key, "worker_calls")) { *value = C.wc_last.bt_calls; return 0; }
-    if (!strcmp(key, "hot_bin_calls")) { *value = C.wc_last.hot_calls; return 0; }
-    if (!strcmp(key, "positions")) { *value = C.stats.positions; return 0; }
+    if (compress_counter(key, C.prof_last, C.wc_last, C.stats.positions, value)) return 0;
     if (!strcmp(key, "block_pool_bytes")) { *value = D.blocks_pool_size; return 0; }
     if (!strcmp(key, "block_redo_streams")) { *value = D.redo_streams; return 0; }
     if (!strcmp(key, "gpu_max_hw_queues_effective")) { *value = (uint64_t)g_hwq_effective; return 0; }
@@ -1455,7 +1350,7 @@ static int blocks_step_impl(DevState &D, uint32_t max_chunks_per_block, uint64_t
 {
     Ctx &C = D.ctx;
     const size_t nj = D.jobs.size();
-    hipEvent_t e0 = C.ev[0][5], e1 = C.ev[0][6];
+    hipEvent_t e0 = C.ev[0][kEvCallBegin], e1 = C.ev[0][kEvCallEnd];
     HIPCHK(hipEventRecord(e0, C.st));
     HIPCHK(hipStreamSynchronize(C.st));
     // Rounds: every unfinished stream advances by one launch's worth, and the streams of a round share ONE persistent launch.
@@ -1490,7 +1385,7 @@ static int blocks_step_impl(DevState &D, uint32_t max_chunks_per_block, uint64_t
         for (uint32_t k = 0; k < act.size(); k++) {
             Ctx &c = D.jobs[act[k]].c;
             const StepPlan &P = R.plan[q][act[k]];
-            HIPCHK(hipStreamWaitEvent(gs, c.ev[P.set][6], 0));          // its pre-pass is done
+            HIPCHK(hipStreamWaitEvent(gs, c.ev[P.set][kEvPrepEnd], 0));          // its pre-pass is done
             fill_stream2_args(ph, k, c.g, P.G, P.V, P.c0, P.c1, c.set[P.set].snap);
         }
         HIPCHK(hipMemcpyAsync(pd, ph, stream2_pack_size(), hipMemcpyHostToDevice, gs));
@@ -1596,15 +1491,13 @@ int nlzm_hip_blocks_finish(void *d_dst, uint64_t dst_cap, uint64_t *block_len, u
     }
     if (D.opt.report) {
         // which stage limits a stream under load: smallest / median / largest over the streams, cycles per position
-        static const char *const what[8] = { "finder total", "finder waiting", "  of it for BT4 results", "table stage total", "table stage waiting",
-                                             "parser total", "parser waiting (records)", "parser passes" };
         fprintf(stderr, "block set of %zu streams, %lld worker CUs each -- per stream, cycles per position (min / median / max over the streams):\n", D.jobs.size(), (long long)D.blocks_wb);
         for (int k = 0; k < 8; k++) {
             std::vector<double> v;
             for (auto &j : D.jobs) if (!j.rc) v.push_back(j.c.acct[k]);
             if (v.empty()) continue;
             std::sort(v.begin(), v.end());
-            fprintf(stderr, "  %-26s %8.0f %8.0f %8.0f\n", what[k], v.front(), v[v.size() / 2], v.back());
+            fprintf(stderr, "  %-26s %8.0f %8.0f %8.0f\n", kAcctRows[k].label, v.front(), v[v.size() / 2], v.back());
         }
     }
     int rc = 0;

@@ -899,11 +899,11 @@ __device__ __forceinline__ void worker_role_hot(const Geom &g, const Globals &G,
         uint32_t kc = 0;
         while (kc < 7 && (k_total >> (14 + kc))) kc++;
         unsigned long long *hc = G.wcnt->hot_class[kc];
-        atomicAdd(&hc[0], 1ull); atomicAdd(&hc[1], t_calls); atomicAdd(&hc[2], n_tests); atomicAdd(&hc[3], (unsigned long long)n_steps); atomicAdd(&hc[4], (unsigned long long)k_work);
-        atomicAdd(&hc[5], (unsigned long long)k_tests); atomicAdd(&hc[6], (unsigned long long)k_rep); atomicAdd(&hc[7], (unsigned long long)k_rec); atomicAdd(&hc[8], (unsigned long long)k_full); atomicAdd(&hc[9], (unsigned long long)k_blk);
-        atomicAdd(&hc[10], (unsigned long long)k_noent); atomicAdd(&hc[11], (unsigned long long)(__builtin_readcyclecounter() - k_t0)); atomicAdd(&hc[12], t_skip); atomicAdd(&hc[13], (unsigned long long)k_und);
+        atomicAdd(&hc[kHcWaves], 1ull); atomicAdd(&hc[kHcCalls], t_calls); atomicAdd(&hc[kHcTests], n_tests); atomicAdd(&hc[kHcSteps], (unsigned long long)n_steps); atomicAdd(&hc[kHcTestSteps], (unsigned long long)k_work);
+        atomicAdd(&hc[kHcLaneTests], (unsigned long long)k_tests); atomicAdd(&hc[kHcRepeats], (unsigned long long)k_rep); atomicAdd(&hc[kHcTakingBack], (unsigned long long)k_rec); atomicAdd(&hc[kHcAllHold], (unsigned long long)k_full); atomicAdd(&hc[kHcMayNotStart], (unsigned long long)k_blk);
+        atomicAdd(&hc[kHcNoEntry], (unsigned long long)k_noent); atomicAdd(&hc[kHcCycles], (unsigned long long)(__builtin_readcyclecounter() - k_t0)); atomicAdd(&hc[kHcSkipped], t_skip); atomicAdd(&hc[kHcIdleUndecided], (unsigned long long)k_und);
 #ifdef NLZM_PROFILE
-        for (int z = 0; z < 7; z++) atomicAdd(&hc[14 + z], t_sec[z]);
+        for (uint32_t z = 0; z < kHcSecN; z++) atomicAdd(&hc[kHcSec + z], t_sec[z]);
 #endif
     }
 #undef NLZM_HOT_STAMP

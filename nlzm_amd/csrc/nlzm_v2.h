@@ -62,9 +62,15 @@ struct Hx {                                     // progress words, one 128-byte 
     alignas(128) uint32_t ext_cur;              // worker lanes: extension blocks of pair lists taken in this launch (Globals::bt_ext_cur)
     alignas(128) uint32_t err;                  // any stage: nonzero -> every stage leaves (the FIRST code stays: raise())
     uint32_t err_info[7];                       // of the stage that raised it: stage (11 finder, 12 table, 13 parser), wait site, position, what it saw
-    alignas(128) uint32_t dbg[4][32];           // per stage (0 finder, 1 table, 2 parser): where it was when it left because of an error
+    alignas(128) uint32_t dbg[4][32];           // per stage (DbgRow): where it was when it left because of an error, word by word below
 };
 enum : uint32_t { kStFinder = 11, kStTable = 12, kStParser = 13 };
+enum DbgRow : uint32_t { kDbgFinder = 0, kDbgTable = 1, kDbgParser = 2 };
+// the words of a stage's row of Hx::dbg
+enum DbgFinderWord : uint32_t { kDfBlock, kDfReach, kDfTopActive, kDfTopDist, kDfTopEnd, kDfPrevNice, kDfSegStart, kDfRkLen, kDfTPosSeen, kDfErr, kDfBase, kDfWords };
+enum DbgTableWord : uint32_t { kDtCursor, kDtTurn, kDtCarrySeq, kDtFSeen, kDtPSeen, kDtCarryN, kDtWords };
+enum DbgParserWord : uint32_t { kDpChunk, kDpSegment, kDpBlockNode, kDpMaxParse, kDpStaged, kDpTOutSeen, kDpErr, kDpWords };
+static_assert(kDfWords == 11 && kDtWords == 6 && kDpWords == 7, "Hx::dbg rows");
 // What the host looks at after a launch, copied aside on the device when the next launch is already queued behind it (block mode)
 struct RoundSnap { uint32_t error, next_chunk, aborted, pad; Hx hx; };
 
@@ -225,7 +231,7 @@ struct Finder {
     unsigned long long t_wait, t_wait_bt = 0, t_total;
     uint32_t n_so_top = 0, n_so_tie = 0, n_so_won = 0;  // cut-short RK256 entries that became the growing top entry; that ended exactly where another entry ends; and won that
     uint32_t n_late_unc = 0, n_late_other = 0, n_late_hot = 0, n_late_first = 0, n_late_blocks = 0;
-    unsigned long long t_f[8] = {};             // profile build: cycles per section of block()
+    unsigned long long t_f[kPfFinderSecN] = {}; // profile build: cycles per section of block()
 #ifdef NLZM_PROFILE
     XW_FN unsigned long long ptick() const { return xw::tick(); }
 #else
@@ -880,22 +886,22 @@ struct Finder {
             xw::atomic_add64_agent(&c.rk_probes, n_rkp); xw::atomic_add64_agent(&c.rk_inserts, n_rki);
             xw::atomic_add64_agent(&c.cmp_bytes, n_cmp); xw::atomic_add64_agent(&c.shifts, shifts);
             unsigned long long *pr = P->prof;
-            xw::atomic_add64_agent(&pr[0], n_blocks); xw::atomic_add64_agent(&pr[1], n_cut0); xw::atomic_add64_agent(&pr[2], n_cut1);
-            xw::atomic_add64_agent(&pr[3], n_cut2); xw::atomic_add64_agent(&pr[4], n_cut3); xw::atomic_add64_agent(&pr[5], n_cut4);
-            xw::atomic_add64_agent(&pr[12], n_cut5);
-            xw::atomic_add64_agent(&pr[16], t_wait); xw::atomic_add64_agent(&pr[17], xw::tick() - t_start); xw::atomic_add64_agent(&pr[25], t_wait_bt);
-            xw::atomic_add64_agent(&pr[28], n_late_unc); xw::atomic_add64_agent(&pr[29], n_late_other);
-            xw::atomic_add64_agent(&pr[115], n_so_top); xw::atomic_add64_agent(&pr[116], n_so_tie); xw::atomic_add64_agent(&pr[117], n_so_won);
-            xw::atomic_add64_agent(&pr[118], n_seg_own); xw::atomic_add64_agent(&pr[119], n_seg_wait);
-            xw::atomic_add64_agent(&pr[110], n_late_hot); xw::atomic_add64_agent(&pr[111], n_late_first); xw::atomic_add64_agent(&pr[112], n_late_blocks);
+            xw::atomic_add64_agent(&pr[kPfFinderBlocks], n_blocks); xw::atomic_add64_agent(&pr[kPfFinderCutNice], n_cut0); xw::atomic_add64_agent(&pr[kPfFinderCutTop], n_cut1);
+            xw::atomic_add64_agent(&pr[kPfFinderCutRkCand], n_cut2); xw::atomic_add64_agent(&pr[kPfFinderCutRkCatchUp], n_cut3); xw::atomic_add64_agent(&pr[kPfFinderCutOther], n_cut4);
+            xw::atomic_add64_agent(&pr[kPfFinderCutBin], n_cut5);
+            xw::atomic_add64_agent(&pr[kPfFinderWait], t_wait); xw::atomic_add64_agent(&pr[kPfFinderTotal], xw::tick() - t_start); xw::atomic_add64_agent(&pr[kPfFinderWaitBt], t_wait_bt);
+            xw::atomic_add64_agent(&pr[kPfFinderLateUnc], n_late_unc); xw::atomic_add64_agent(&pr[kPfFinderLateOther], n_late_other);
+            xw::atomic_add64_agent(&pr[kPfRkShortTop], n_so_top); xw::atomic_add64_agent(&pr[kPfRkShortTie], n_so_tie); xw::atomic_add64_agent(&pr[kPfRkShortWon], n_so_won);
+            xw::atomic_add64_agent(&pr[kPfFinderSegOwn], n_seg_own); xw::atomic_add64_agent(&pr[kPfFinderSegWait], n_seg_wait);
+            xw::atomic_add64_agent(&pr[kPfFinderLateHot], n_late_hot); xw::atomic_add64_agent(&pr[kPfFinderLateFirst], n_late_first); xw::atomic_add64_agent(&pr[kPfFinderLateBlocks], n_late_blocks);
 #ifdef NLZM_PROFILE
-            for (int z = 0; z < 8; z++) xw::atomic_add64_agent(&pr[88 + z], t_f[z]);
+            for (uint32_t z = 0; z < kPfFinderSecN; z++) xw::atomic_add64_agent(&pr[kPfFinderSec + z], t_f[z]);
 #endif
             if (err || xw::ld_agent(&V.hx->err)) {                  // where this stage was when it left
-                uint32_t *d = V.hx->dbg[0];
-                xw::st_agent(d + 0, dbg_a); xw::st_agent(d + 1, reach); xw::st_agent(d + 2, s_active); xw::st_agent(d + 3, s_d);
-                xw::st_agent(d + 4, s_end); xw::st_agent(d + 5, prev_nice); xw::st_agent(d + 6, seg_s); xw::st_agent(d + 7, rk_len);
-                xw::st_agent(d + 8, t_pos_seen); xw::st_agent(d + 9, err); xw::st_agent(d + 10, base);
+                uint32_t *d = V.hx->dbg[kDbgFinder];
+                xw::st_agent(&d[kDfBlock], dbg_a); xw::st_agent(&d[kDfReach], reach); xw::st_agent(&d[kDfTopActive], s_active); xw::st_agent(&d[kDfTopDist], s_d);
+                xw::st_agent(&d[kDfTopEnd], s_end); xw::st_agent(&d[kDfPrevNice], prev_nice); xw::st_agent(&d[kDfSegStart], seg_s); xw::st_agent(&d[kDfRkLen], rk_len);
+                xw::st_agent(&d[kDfTPosSeen], t_pos_seen); xw::st_agent(&d[kDfErr], err); xw::st_agent(&d[kDfBase], base);
             }
         }
     }
@@ -1305,18 +1311,19 @@ struct Table {
         if (err && i == 0) raise(V.hx, kErrInternal + 200, kStTable, 9, xw::lds_ld(&L->cursor));   // (only if no stage has raised anything: the first code stays)
         xw::block_sync();
         if (w == 0 && i == 0 && xw::ld_agent(&V.hx->err)) {     // where this stage was when it left
-            uint32_t *d = V.hx->dbg[1];
-            xw::st_agent(d + 0, xw::lds_ld(&L->cursor)); xw::st_agent(d + 1, xw::lds_ld(&L->turn)); xw::st_agent(d + 2, xw::lds_ld(&L->carry_seq));
-            xw::st_agent(d + 3, f_seen); xw::st_agent(d + 4, p_seen); xw::st_agent(d + 5, L->carry_n);
+            uint32_t *d = V.hx->dbg[kDbgTable];
+            xw::st_agent(&d[kDtCursor], xw::lds_ld(&L->cursor)); xw::st_agent(&d[kDtTurn], xw::lds_ld(&L->turn)); xw::st_agent(&d[kDtCarrySeq], xw::lds_ld(&L->carry_seq));
+            xw::st_agent(&d[kDtFSeen], f_seen); xw::st_agent(&d[kDtPSeen], p_seen); xw::st_agent(&d[kDtCarryN], L->carry_n);
         }
         if (i == 0) {       // accounting: summed over the waves
             unsigned long long *pr = G.persist->prof;
-            xw::atomic_add64_agent(&pr[6], n_blocks); xw::atomic_add64_agent(&pr[7], n_slow);
-            xw::atomic_add64_agent(&pr[105], n_fr8); xw::atomic_add64_agent(&pr[106], n_fr12); xw::atomic_add64_agent(&pr[107], n_fr16);
-            xw::atomic_add64_agent(&pr[108], n_fr20); xw::atomic_add64_agent(&pr[109], n_fr24);
-            xw::atomic_add64_agent(&pr[44], tt0); xw::atomic_add64_agent(&pr[45], tt1);
-            xw::atomic_add64_agent(&pr[46], tt2); xw::atomic_add64_agent(&pr[47], tt3); xw::atomic_add64_agent(&pr[55], tt4);
-            if (w == 0) { xw::atomic_add64_agent(&pr[18], t_wait); xw::atomic_add64_agent(&pr[19], xw::tick() - t_start); }
+            static_assert(kPfTableFrontN == 5, "n_fr8 .. n_fr24");
+            xw::atomic_add64_agent(&pr[kPfTableBlocks], n_blocks); xw::atomic_add64_agent(&pr[kPfTableSlowBlocks], n_slow);
+            xw::atomic_add64_agent(&pr[kPfTableFront + 0], n_fr8); xw::atomic_add64_agent(&pr[kPfTableFront + 1], n_fr12); xw::atomic_add64_agent(&pr[kPfTableFront + 2], n_fr16);
+            xw::atomic_add64_agent(&pr[kPfTableFront + 3], n_fr20); xw::atomic_add64_agent(&pr[kPfTableFront + 4], n_fr24);
+            xw::atomic_add64_agent(&pr[kPfTableGather], tt0); xw::atomic_add64_agent(&pr[kPfTableScan], tt1);
+            xw::atomic_add64_agent(&pr[kPfTableMerge], tt2); xw::atomic_add64_agent(&pr[kPfTableCarryWait], tt3); xw::atomic_add64_agent(&pr[kPfTableRecords], tt4);
+            if (w == 0) { xw::atomic_add64_agent(&pr[kPfTableWait], t_wait); xw::atomic_add64_agent(&pr[kPfTableTotal], xw::tick() - t_start); }
         }
         if (w == 0) {
             const uint32_t on = xw::readfirst(L->carry_n);
@@ -1334,8 +1341,8 @@ struct Table {
                 if (wide && ns < (nb >> kTbNarrowShift)) nxt = 0;
                 if (G.table_shape) nxt = G.table_shape - 1;        // (option `table_shape`: 1 narrow, 2 wide; 0: by the data)
                 S->tb_wide[(G.launch_par & 1u) ^ 1u] = nxt;
-                if (nxt != wide) xw::atomic_add64_agent(&G.persist->prof[113], 1ull);
-                if (wide) xw::atomic_add64_agent(&G.persist->prof[114], 1ull);
+                if (nxt != wide) xw::atomic_add64_agent(&G.persist->prof[kPfTableShapeChanges], 1ull);
+                if (wide) xw::atomic_add64_agent(&G.persist->prof[kPfTableWideLaunches], 1ull);
             }
         }
     }
@@ -1458,7 +1465,7 @@ struct Parser {
     uint32_t err;
     uint32_t n_eq_fill, n_eq_rounds;            // (per launch)
     uint32_t n_cmp;                             // (per lane and launch: well below 2^32)
-    unsigned long long t_s[7] = {}, t_q[5] = {};
+    unsigned long long t_s[kPfParserSecN] = {}, t_q[kPfParserLoaderSecN] = {};
     // the stage's accounting lives in LDS (L()->acc: it is touched once a block or less, and scalar registers are short)
     enum { kAccWait, kAccEmit, kAccSetup, kAccPass, kAccBlocks, kAccPasses, kAccRedo, kAccUndo, kAccTotal, kAccNeed, kAccAhead, kAccJobs, kAccTaken, kAccTakenNodes, kAccHelpWait, kAccN };
     XW_FN void acc(uint32_t k, unsigned long long v) { if (xw::lane() == 0) xw::lds_add64(&L()->acc[k], v); }
@@ -2570,13 +2577,14 @@ struct Parser {
         if (V.hb && tid == 0) xw::st_agent(&V.hx->h_job, kHelpExit);      // (the helper leaves)
         xw::block_sync();
 #ifdef NLZM_PROFILE
-        if (xw::lane() == 0 && xw::wave() == kPW - 1) for (int z = 0; z < 5; z++) xw::atomic_add64_agent(&P->prof[56 + z], t_q[z]);
-        if (xw::lane() == 0) { xw::atomic_add64_agent(&P->prof[64 + xw::wave()], t_work); xw::atomic_add64_agent(&P->prof[72 + xw::wave()], t_bar); xw::atomic_add64_agent(&P->prof[80 + xw::wave()], t_upd); }
-        if (xw::lane() == 0 && xw::wave() < 4) {   // per wave: relax + probe work of a pass, barrier wait, update; mask fills
-            xw::atomic_add64_agent(&P->prof[32 + xw::wave()], t_work); xw::atomic_add64_agent(&P->prof[36 + xw::wave()], t_bar);
+        static_assert(kPW == kPfParserAllN, "a slot per wave");
+        if (xw::lane() == 0 && xw::wave() == kPW - 1) for (uint32_t z = 0; z < kPfParserLoaderSecN; z++) xw::atomic_add64_agent(&P->prof[kPfParserLoaderSec + z], t_q[z]);
+        if (xw::lane() == 0) { xw::atomic_add64_agent(&P->prof[kPfParserAllWork + xw::wave()], t_work); xw::atomic_add64_agent(&P->prof[kPfParserAllBar + xw::wave()], t_bar); xw::atomic_add64_agent(&P->prof[kPfParserAllUpdate + xw::wave()], t_upd); }
+        if (xw::lane() == 0 && xw::wave() < kPfParserWaveN) {   // per wave: relax + probe work of a pass, barrier wait, update; mask fills
+            xw::atomic_add64_agent(&P->prof[kPfParserWaveWork + xw::wave()], t_work); xw::atomic_add64_agent(&P->prof[kPfParserWaveBar + xw::wave()], t_bar);
             if (xw::wave() == 0) {
-                xw::atomic_add64_agent(&P->prof[40], t_upd); xw::atomic_add64_agent(&P->prof[42], t_fin); xw::atomic_add64_agent(&P->prof[41], t_fill);
-                for (int z = 0; z < 7; z++) { xw::atomic_add64_agent(&P->prof[48 + z], t_s[z]); t_s[z] = 0; }
+                xw::atomic_add64_agent(&P->prof[kPfParserUpdate], t_upd); xw::atomic_add64_agent(&P->prof[kPfParserBlockEnd], t_fin); xw::atomic_add64_agent(&P->prof[kPfParserFill], t_fill);
+                for (uint32_t z = 0; z < kPfParserSecN; z++) { xw::atomic_add64_agent(&P->prof[kPfParserSec + z], t_s[z]); t_s[z] = 0; }
             }
         }
 #endif
@@ -2597,20 +2605,20 @@ struct Parser {
                 // (this stage's counters only, agent-scope atomics: see the finder's)
                 unsigned long long *pr = P->prof;
                 auto add = [](unsigned long long *q, unsigned long long v) __attribute__((always_inline)) { xw::atomic_add64_agent(q, v); };
-                add(&pr[8], L()->acc[kAccBlocks]); add(&pr[13], L()->acc[kAccPasses]); add(&pr[14], L()->acc[kAccUndo]); add(&pr[26], L()->acc[kAccNeed]); add(&pr[27], L()->acc[kAccAhead]);
-                add(&pr[9], L()->cnt.stale_ht); add(&pr[10], L()->cnt.stale_rk); add(&pr[11], L()->acc[kAccRedo]);
-                add(&pr[96], L()->acc[kAccJobs]); add(&pr[97], L()->acc[kAccTaken]); add(&pr[98], L()->acc[kAccTakenNodes]); add(&pr[99], L()->acc[kAccHelpWait]);
+                add(&pr[kPfParserBlocks], L()->acc[kAccBlocks]); add(&pr[kPfParserPasses], L()->acc[kAccPasses]); add(&pr[kPfParserResampledBack], L()->acc[kAccUndo]); add(&pr[kPfParserNeed], L()->acc[kAccNeed]); add(&pr[kPfParserAhead], L()->acc[kAccAhead]);
+                add(&pr[kPfParserMaskFills], L()->cnt.stale_ht); add(&pr[kPfParserProbeRounds], L()->cnt.stale_rk); add(&pr[kPfParserResampled], L()->acc[kAccRedo]);
+                add(&pr[kPfHelpJobs], L()->acc[kAccJobs]); add(&pr[kPfHelpTaken], L()->acc[kAccTaken]); add(&pr[kPfHelpTakenNodes], L()->acc[kAccTakenNodes]); add(&pr[kPfHelpWait], L()->acc[kAccHelpWait]);
                 Counters &c = P->cnt;
                 const Counters &lc = L()->cnt;
                 add(&c.n_literal, lc.n_literal); add(&c.n_dict, lc.n_dict); add(&c.n_rep, lc.n_rep); add(&c.segments, lc.segments);
                 add(&c.rans_syms, lc.rans_syms); add(&c.bit_ops, lc.bit_ops); add(&c.frames, lc.frames); add(&c.cmp_bytes, lc.cmp_bytes);
-                add(&pr[20], L()->acc[kAccWait]); add(&pr[21], L()->acc[kAccTotal] + xw::tick()); add(&pr[22], L()->acc[kAccEmit]); add(&pr[23], L()->acc[kAccSetup]); add(&pr[24], L()->acc[kAccPass]);
+                add(&pr[kPfParserWait], L()->acc[kAccWait]); add(&pr[kPfParserTotal], L()->acc[kAccTotal] + xw::tick()); add(&pr[kPfParserEmit], L()->acc[kAccEmit]); add(&pr[kPfParserSetup], L()->acc[kAccSetup]); add(&pr[kPfParserPass], L()->acc[kAccPass]);
                 const uint32_t xe = xw::ld_agent(&V.hx->err);
                 if (xe) {                                           // (this stage is the only writer of the sticky error word)
                     P->error = xe;
-                    uint32_t *d = V.hx->dbg[2];                     // where this stage was when it left
-                    xw::st_agent(d + 0, ci); xw::st_agent(d + 1, L()->dbgw[0]); xw::st_agent(d + 2, L()->dbgw[1]); xw::st_agent(d + 3, L()->dbgw[2]);
-                    xw::st_agent(d + 4, L()->stg[4]); xw::st_agent(d + 5, t_out_seen); xw::st_agent(d + 6, err);
+                    uint32_t *d = V.hx->dbg[kDbgParser];            // where this stage was when it left
+                    xw::st_agent(&d[kDpChunk], ci); xw::st_agent(&d[kDpSegment], L()->dbgw[0]); xw::st_agent(&d[kDpBlockNode], L()->dbgw[1]); xw::st_agent(&d[kDpMaxParse], L()->dbgw[2]);
+                    xw::st_agent(&d[kDpStaged], L()->stg[4]); xw::st_agent(&d[kDpTOutSeen], t_out_seen); xw::st_agent(&d[kDpErr], err);
                 }
                 if ((err || xe) && G.abort_word) xw::st_agent(G.abort_word, 1u);
             }
@@ -2679,9 +2687,9 @@ struct Parser {
         xw::block_sync();
         if (tid == 0) {
             unsigned long long *pr = G.persist->prof;
-            xw::atomic_add64_agent(&pr[100], L()->acc[kAccJobs]); xw::atomic_add64_agent(&pr[101], L()->acc[kAccTaken]);
-            xw::atomic_add64_agent(&pr[102], L()->acc[kAccBlocks]); xw::atomic_add64_agent(&pr[103], L()->acc[kAccPasses]);
-            xw::atomic_add64_agent(&pr[104], L()->acc[kAccWait]);
+            xw::atomic_add64_agent(&pr[kPfHelperJobs], L()->acc[kAccJobs]); xw::atomic_add64_agent(&pr[kPfHelperDone], L()->acc[kAccTaken]);
+            xw::atomic_add64_agent(&pr[kPfHelperBlocks], L()->acc[kAccBlocks]); xw::atomic_add64_agent(&pr[kPfHelperPasses], L()->acc[kAccPasses]);
+            xw::atomic_add64_agent(&pr[kPfHelperWait], L()->acc[kAccWait]);
         }
     }
 };

@@ -387,14 +387,17 @@ int main(int argc, char **argv)
         if (nlzm_oracle_compress(in.data(), (uint64_t)n, hb, out.data(), out.size(), &out_n, &st, &hk)) { printf("oracle failed\n"); return 1; }
     }
     const double np = (double)(n ? n : 1);
+    const unsigned long long *p = P.prof;
     printf("finder: %llu blocks (%.1f positions each); cut by: nice %llu, new top entry %llu, RK candidate %llu, RK catch-up %llu, same worker bin %llu, other %llu\n",
-           P.prof[0], np / (double)(P.prof[0] ? P.prof[0] : 1), P.prof[1], P.prof[2], P.prof[3], P.prof[4], P.prof[12], P.prof[5]);
-    printf("cut-short RK256 entries: %llu became the growing top entry, %llu ended where another entry ends (%llu of them the nearer one)\n", P.prof[115], P.prof[116], P.prof[117]);
-    printf("table shape: %llu launches wide, changed %llu times\n", P.prof[114], P.prof[113]);
+           p[kPfFinderBlocks], np / (double)(p[kPfFinderBlocks] ? p[kPfFinderBlocks] : 1), p[kPfFinderCutNice], p[kPfFinderCutTop], p[kPfFinderCutRkCand], p[kPfFinderCutRkCatchUp],
+           p[kPfFinderCutBin], p[kPfFinderCutOther]);
+    printf("cut-short RK256 entries: %llu became the growing top entry, %llu ended where another entry ends (%llu of them the nearer one)\n", p[kPfRkShortTop], p[kPfRkShortTie], p[kPfRkShortWon]);
+    printf("table shape: %llu launches wide, changed %llu times\n", p[kPfTableWideLaunches], p[kPfTableShapeChanges]);
     printf("table: %llu blocks, %llu on the slow path; parser: %llu blocks (%.1f nodes each), %.2f passes per block, mask fills %llu, probe rounds %llu, re-sampled %llu (put back %llu)\n",
-           P.prof[6], P.prof[7], P.prof[8], np / (double)(P.prof[8] ? P.prof[8] : 1), (double)P.prof[13] / (double)(P.prof[8] ? P.prof[8] : 1), P.prof[9], P.prof[10], P.prof[11], P.prof[14]);
+           p[kPfTableBlocks], p[kPfTableSlowBlocks], p[kPfParserBlocks], np / (double)(p[kPfParserBlocks] ? p[kPfParserBlocks] : 1),
+           (double)p[kPfParserPasses] / (double)(p[kPfParserBlocks] ? p[kPfParserBlocks] : 1), p[kPfParserMaskFills], p[kPfParserProbeRounds], p[kPfParserResampled], p[kPfParserResampledBack]);
     printf("helper parser: %llu jobs posted, %llu taken over (%llu nodes), parser waited %llu sweeps for it; helper: %llu jobs seen, %llu done, %llu blocks\n",
-           P.prof[96], P.prof[97], P.prof[98], P.prof[99], P.prof[100], P.prof[101], P.prof[102]);
+           p[kPfHelpJobs], p[kPfHelpTaken], p[kPfHelpTakenNodes], p[kPfHelpWait], p[kPfHelperJobs], p[kPfHelperDone], p[kPfHelperBlocks]);
     printf("workers: uncertain marks %llu (%.2f%%), dry runs %llu\n", unc_total, 100.0 * unc_total / np, wk.dry);
     const int bad = g_ref.bad || c.bad || (g_stop_chunk != 0xFFFFFFFFu ? 0 : 1) * (P.cnt.positions != st.positions || P.cnt.nice_positions != st.nice_positions ||
                     P.cnt.segments != st.segments || P.cnt.bt_tests != st.bt_tests || P.cnt.bt_calls != st.bt_calls ||
