@@ -256,6 +256,36 @@ int nlzm_hip_verify_dev(const void *d_src, uint64_t src_len, uint32_t nblocks, c
 int nlzm_hip_verify(const uint8_t *src, uint64_t src_len, uint32_t nblocks, const uint64_t *block_len,
                     const uint8_t *orig, uint64_t n, uint64_t *first_mismatch, uint64_t *decoded_len);
 
+/* ---- decoding in steps: stop at a frame boundary, resume --------------------------------------------------------------------- */
+/* The same decode, one launch per step: a stream stops in front of a frame header and a later launch picks it up from a record the library keeps
+ * in device memory (nlzm_hip_get_counter("decode_state_bytes") per stream; needs no device) at the price of reloading the last 64 KiB it wrote.  One
+ * decode set is open per device at a time, in the idiom of nlzm_hip_blocks_begin / _step / _finish / _abandon; a second begin closes the set before it.
+ * begin binds the buffers, splits the container (block_len, or the hop over the frame headers when it is NULL) and decodes NOTHING.  Block i's bytes
+ * go to d_dst + sum(raw_len[0..i)), bounded by raw_len[i], as in nlzm_hip_decompress_blocks_dev; raw_len may be NULL for nblocks == 1 only (the bound
+ * is dst_cap then); d_dst == NULL: size-only stepping.  The host form uploads the container, runs the size pass when raw_len is NULL and decodes into
+ * a buffer of the library's own (nlzm_hip_decode_fetch reads it).  flags: NLZM_HIP_DECODE_MORE, for the _dev form with ONE stream: src_len is what
+ * has arrived so far, the caller vouches for nothing behind it, and a step pauses in front of the first frame that is not wholly there;
+ * nlzm_hip_decode_extend_dev says that more has been written behind it (an extend without growth, a step that still pauses for input: the stream
+ * is cut off, and finish answers NLZM_HIP_E_FORMAT).  Any other flag is NLZM_HIP_E_ARG: a prefix read is cut in the middle of an op and cannot resume.
+ * step: ONE launch over the blocks that are neither finished nor at their target (none such: no launch).  Every launched block advances by at most
+ * max_frames frames (0: no limit) and stops at the first frame boundary with at least target[i] bytes decoded (target: nblocks entries or NULL; ~0: to
+ * its end); a stream's terminator ends it whatever the limits.  done[i] (may be NULL): block i's decoded bytes; *finished: every block has reached its
+ * terminator.  A block that ends longer / shorter than its raw_len: NLZM_HIP_E_CAPACITY / NLZM_HIP_E_FORMAT; a step that fails has closed the set.
+ * fetch: off / len address the container's decoded bytes; a part that is not decoded yet, or len > total - off, is NLZM_HIP_E_ARG.
+ * finish needs *finished -- otherwise NLZM_HIP_E_ARG, and the set stays open -- and releases the states; abandon always works.
+ * Counters: after a step the "decode_*" counters are the SET's totals so far (after the last step: the one-shot decode's of the same container),
+ * "decode_steps" its launches, "decode_step_us" the device time of the last step. */
+#define NLZM_HIP_DECODE_MORE 1u
+int nlzm_hip_decode_begin_dev(const void *d_src, uint64_t src_len, uint32_t nblocks, const uint64_t *block_len,
+                              const uint64_t *raw_len, void *d_dst, uint64_t dst_cap, uint32_t flags);
+int nlzm_hip_decode_begin(const uint8_t *src, uint64_t src_len, uint32_t nblocks, const uint64_t *block_len,
+                          const uint64_t *raw_len, uint32_t flags);
+int nlzm_hip_decode_step(uint32_t max_frames, const uint64_t *target, uint64_t *done, int *finished, double *device_ms);
+int nlzm_hip_decode_extend_dev(uint64_t src_len_now);
+int nlzm_hip_decode_fetch(uint64_t off, uint64_t len, uint8_t *dst);
+int nlzm_hip_decode_finish(uint64_t *raw_len_out, uint64_t *dst_len);
+void nlzm_hip_decode_abandon(void);
+
 /* ---- CRC32 of bytes in device memory, and checking a container without its original ------------------------ */
 /* The CRC is the reference's crc32_calc (NLZM.cpp:126-199): reflected polynomial 0xEDB88320, init and final xor 0xFFFFFFFF -- zlib.crc32, and what
  * `nlzm h` prints.  The format stores none; `nlzm c -crc` keeps one per block in the sidecar index (NLZMIDX 2).  A range is cut into segments of

@@ -35,7 +35,11 @@ ABI_SYMBOLS = [
     "nlzm_hip_crc32_dev", "nlzm_hip_crc32", "nlzm_hip_crc32_ranges_dev", "nlzm_hip_crc32_ranges", "nlzm_hip_crc32_combine", "nlzm_hip_feed_input_crc32",
     "nlzm_hip_check_dev", "nlzm_hip_check",
     "nlzm_hip_read_ranges_dev", "nlzm_hip_read_ranges",
+    "nlzm_hip_decode_begin_dev", "nlzm_hip_decode_begin", "nlzm_hip_decode_step", "nlzm_hip_decode_extend_dev", "nlzm_hip_decode_fetch",
+    "nlzm_hip_decode_finish", "nlzm_hip_decode_abandon",
 ]
+DECODE_MORE = 1          # NLZM_HIP_DECODE_MORE
+TO_THE_END = (1 << 64) - 1
 
 
 class NlzmError(RuntimeError):
@@ -134,6 +138,14 @@ def load_library() -> C.CDLL:
     lib.nlzm_hip_check.argtypes = [C.c_void_p, C.c_uint64, C.c_uint32, u64p, u64p, u32p, u32p, u32p]
     lib.nlzm_hip_read_ranges_dev.argtypes = [C.c_void_p, C.c_uint64, C.c_uint32, u64p, u64p, u32p, C.c_uint32, u64p, u64p, C.c_void_p, C.c_uint64, u64p, u32p]
     lib.nlzm_hip_read_ranges.argtypes = [C.c_void_p, C.c_uint64, C.c_uint32, u64p, u64p, u32p, C.c_uint32, u64p, u64p, C.c_void_p, C.c_uint64, u64p, u32p]
+    if hasattr(lib, "nlzm_hip_decode_begin"):      # (absent from older diagnostic builds loaded through NLZM_LIB)
+        lib.nlzm_hip_decode_begin_dev.argtypes = [C.c_void_p, C.c_uint64, C.c_uint32, u64p, u64p, C.c_void_p, C.c_uint64, C.c_uint32]
+        lib.nlzm_hip_decode_begin.argtypes = [C.c_void_p, C.c_uint64, C.c_uint32, u64p, u64p, C.c_uint32]
+        lib.nlzm_hip_decode_step.argtypes = [C.c_uint32, u64p, u64p, C.POINTER(C.c_int), C.POINTER(C.c_double)]
+        lib.nlzm_hip_decode_extend_dev.argtypes = [C.c_uint64]
+        lib.nlzm_hip_decode_fetch.argtypes = [C.c_uint64, C.c_uint64, C.c_void_p]
+        lib.nlzm_hip_decode_finish.argtypes = [u64p, u64p]
+        lib.nlzm_hip_decode_abandon.restype = None
     _lib = lib
     return lib
 
@@ -377,6 +389,79 @@ def read_ranges(blob, ranges, nblocks: int = 1, block_lens=None, raw_lens=None, 
 def read_range(blob, off: int, length: int, nblocks: int = 1, block_lens=None, raw_lens=None, crcs=None) -> bytes:
     """read_ranges for one range"""
     return read_ranges(blob, [(off, length)], nblocks, block_lens, raw_lens, crcs)[0]
+
+
+class Decoder:
+    """A block container (nblocks streams back to back) decoded in steps on the device: every step is one launch that takes the blocks it
+    concerns to a frame boundary, where they stay at rest in a record the library keeps until a later step picks them up.  The container is
+    uploaded once and decoded into a buffer of the library's; read() fetches from it.  One Decoder is open at a time (a new one closes the
+    one before it); a context manager: leaving it abandons what is not finished.  Without raw_lens the blocks are sized first (a pass of its own)."""
+
+    def __init__(self, blob, nblocks: int = 1, block_lens=None, raw_lens=None):
+        lib = load_library()
+        src = _bytes_in(blob)
+        for name, v in (("block_lens", block_lens), ("raw_lens", raw_lens)):
+            if v is not None and len(v) != nblocks:
+                raise ValueError(f"{name}: one entry per block")
+        blen = (C.c_uint64 * nblocks)(*[int(x) for x in block_lens]) if block_lens is not None else None
+        raw = (C.c_uint64 * nblocks)(*[int(x) for x in raw_lens]) if raw_lens is not None else None
+        if raw is None:          # (the lengths are wanted here too: read() addresses the decoded bytes)
+            raw, total = (C.c_uint64 * nblocks)(), C.c_uint64(0)
+            _chk(lib.nlzm_hip_decompress_blocks(src.ctypes.data, src.size, nblocks, blen, None, None, 0, raw, C.byref(total)))
+        self.nblocks = nblocks
+        self.raw_lens = [int(x) for x in raw]
+        self.starts = [sum(self.raw_lens[:i]) for i in range(nblocks)]
+        self.done = [0] * nblocks
+        self.finished = False
+        self.device_ms = 0.0
+        _chk(lib.nlzm_hip_decode_begin(src.ctypes.data, src.size, nblocks, blen, raw, 0))
+        self._open = True
+
+    def step(self, max_frames: int = 0, targets=None):
+        """One launch: every block that is neither finished nor at its target advances by at most max_frames frames (0: no limit) and stops at
+        the first frame boundary with targets[i] bytes decoded (None, or TO_THE_END: at its end).  (done, finished)."""
+        if not self._open:
+            raise NlzmError("the decoder is closed")
+        if targets is not None and len(targets) != self.nblocks:
+            raise ValueError("targets: one entry per block")
+        tg = (C.c_uint64 * self.nblocks)(*[min(int(t), TO_THE_END) for t in targets]) if targets is not None else None
+        done, fin, ms = (C.c_uint64 * self.nblocks)(), C.c_int(0), C.c_double(0)
+        rc = load_library().nlzm_hip_decode_step(max_frames, tg, done, C.byref(fin), C.byref(ms))
+        if rc:
+            self._open = False       # (a failing step has closed the set)
+            _chk(rc)
+        self.done, self.finished, self.device_ms = [int(x) for x in done], bool(fin.value), self.device_ms + ms.value
+        return list(self.done), self.finished
+
+    def read(self, off: int, length: int) -> bytes:
+        """`length` decoded bytes from offset `off` of the container's content: exactly the blocks the range intersects advance, each up to the
+        range's end in it (one step), and the bytes are fetched.  A later read further on in a block goes on where this one stopped."""
+        total = sum(self.raw_lens)
+        if off < 0 or length < 0 or off > total or length > total - off:
+            raise ValueError("the range runs over the container's decoded bytes")
+        if not length:
+            return b""
+        targets = list(self.done)
+        for i, (lo, n) in enumerate(zip(self.starts, self.raw_lens)):
+            if lo < off + length and off < lo + n:
+                targets[i] = max(targets[i], min(off + length, lo + n) - lo)
+        if any(t > d for t, d in zip(targets, self.done)):
+            self.step(0, targets)
+        dst = np.empty(length, dtype=np.uint8)
+        _chk(load_library().nlzm_hip_decode_fetch(off, length, dst.ctypes.data))
+        return dst.tobytes()
+
+    def close(self) -> None:
+        if self._open:
+            load_library().nlzm_hip_decode_abandon()
+            self._open = False
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+        return False
 
 
 def read_index(path):

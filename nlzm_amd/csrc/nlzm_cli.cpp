@@ -15,6 +15,7 @@
 #include <stdlib.h>
 #include <string.h>
 #include <time.h>
+#include <unistd.h>
 
 #include <exception>
 #include <thread>
@@ -262,6 +263,7 @@ int main(int argc, char **argv)
     bool verify = false;                            // -verify (not in the reference): c decodes what it wrote on the device and compares it with the input
     bool with_crc = false;                          // -crc (not in the reference): c keeps every block's CRC32, hashed on the device, in the index (NLZMIDX 2); d / t check them
     bool on_gpu = false;                            // -gpu (not in the reference): d / t decode on the device; without it they are host-only and need none
+    uint32_t steps_k = 0;                           // -steps:K (not in the reference): d -gpu / t -gpu decode in steps of K frames per block
     std::vector<ByteRange> ranges;                  // -range:off:len (not in the reference): what x writes, in this order
     while (argc >= 2 && *argv[1] == '-') {
         char *arg = argv[1];
@@ -286,6 +288,14 @@ int main(int argc, char **argv)
             with_crc = true;
         } else if (!strcmp(arg, "gpu")) {
             on_gpu = true;
+        } else if (!strncmp(arg, "steps:", 6)) {
+            // digits and nothing else, 1 .. 2^32 - 1 (as strict as -range:)
+            unsigned long long v = 0;
+            const char *p = arg + 6;
+            bool ok = *p >= '0' && *p <= '9';
+            for (; ok && *p >= '0' && *p <= '9'; p++) { v = v * 10 + (unsigned long long)(*p - '0'); if (v > 0xFFFFFFFFull) ok = false; }
+            if (!ok || *p || v < 1) { printf("Unrecognized flag %s\n", arg); return -1; }
+            steps_k = (uint32_t)v;
         } else if (!strncmp(arg, "range:", 6)) {
             // digits ':' digits and nothing else; a number that does not fit 64 bits is refused, not saturated
             auto number = [](const char *&p, unsigned long long &v) {
@@ -306,6 +316,7 @@ int main(int argc, char **argv)
         }
     }
     const int cmd = argc >= 2 ? (argv[1][0] | 0x20) : 0;
+    if (steps_k && !(on_gpu && ((argc == 4 && cmd == 'd') || (argc == 3 && cmd == 't')))) { printf("Error: -steps:K is for d -gpu and t -gpu\n"); return -1; }
     if (argc == 4 && cmd == 'c') {
         if (FILE *probe = fopen(argv[3], "rb")) { printf("Error: %s already exists\n", argv[3]); fclose(probe); return -1; }
         const bool one_stream = !ngpus && nblocks == 1 && !verify;      // (-verify needs input and stream whole: the one-call path)
@@ -540,7 +551,52 @@ int main(int argc, char **argv)
             out.clear(); got_crcs.clear(); out_on_device = false; out_size = 0;
             rc = parts.empty() ? -3 : 0;
             bool index_wrong = false;               // a block did not decode to the bytes its index entry says it holds
-            if (!rc && on_gpu && idx_has_crc && cmd == 't') {
+            if (!rc && on_gpu && steps_k) {
+                // the same decode in steps of K frames per block (nlzm_hip_decode_*): after every step each block's new bytes are fetched, hashed and --
+                // d -- written at the block's offset, so the host holds one step's output at a time
+                const uint32_t k = (uint32_t)parts.size();
+                std::vector<uint64_t> blen(k), raw(k), at(k, 0), done(k, 0), had(k, 0);
+                for (uint32_t i = 0; i < k; i++) blen[i] = parts[i].n;
+                const uint64_t src_len = (uint64_t)(parts.back().p + parts.back().n - parts[0].p);
+                uint64_t total = 0, launches = 0;
+                int drc = 0;
+                if (by_index) raw = raws;
+                else drc = nlzm_hip_decompress_blocks(parts[0].p, src_len, k, blen.data(), nullptr, nullptr, 0, raw.data(), &total);      // (no lengths anywhere in the format: a size pass)
+                for (uint32_t i = 1; i < k; i++) at[i] = at[i - 1] + raw[i - 1];
+                if (!drc) drc = nlzm_hip_decode_begin(parts[0].p, src_len, k, blen.data(), raw.data(), 0);
+                std::vector<uint32_t> crcs(k, 0);
+                std::vector<uint8_t> piece;
+                int finished = 0;
+                bool open = !drc;
+                while (!drc && !finished) {
+                    drc = nlzm_hip_decode_step(steps_k, nullptr, done.data(), &finished, nullptr);
+                    if (drc) { open = false; break; }           // (a failing step has closed the set)
+                    for (uint32_t i = 0; i < k && !drc; i++) {
+                        const uint64_t n = done[i] - had[i];
+                        if (!n) continue;
+                        piece.resize((size_t)n);
+                        drc = nlzm_hip_decode_fetch(at[i] + had[i], n, piece.data());
+                        if (drc) break;
+                        crcs[i] = crc_calc(piece.data(), n, crcs[i]);
+                        if (fout) { fseeko(fout, (off_t)(at[i] + had[i]), SEEK_SET); fwrite(piece.data(), 1, (size_t)n, fout); }
+                        had[i] = done[i];
+                    }
+                }
+                if (!drc) { (void)nlzm_hip_get_counter("decode_steps", &launches); drc = nlzm_hip_decode_finish(nullptr, &total); open = false; }
+                if (open) nlzm_hip_decode_abandon();
+                if (by_index && (drc == NLZM_HIP_E_CAPACITY || drc == NLZM_HIP_E_FORMAT || drc == NLZM_HIP_E_NOMEM)) { index_wrong = true; drc = 0; }
+                if (drc == NLZM_HIP_E_FORMAT) rc = -7;
+                else if (drc) { printf("Error: %s\n", nlzm_hip_last_error()); if (fout) { fclose(fout); remove(argv[3]); } return -1; }
+                hb = parts[0].p[1]; fb = parts[0].p[3];
+                // (a decode that did not come to its end leaves nothing of what its steps wrote: the one-call path writes nothing then either)
+                if ((index_wrong || rc) && fout) { fflush(fout); if (ftruncate(fileno(fout), 0)) {} fseeko(fout, 0, SEEK_SET); }
+                if (!index_wrong && !rc) {
+                    if (k > 1) printf("Blocks: %d\n", (int)k);
+                    printf("Steps: %u frames, %" PRIu64 " launches\n", steps_k, launches);
+                    if (fout) { fflush(fout); if (ftruncate(fileno(fout), (off_t)total)) {} fseeko(fout, 0, SEEK_END); }
+                    raws = raw; got_crcs = crcs; out_size = total; out_on_device = true;        // (nothing of the output is left on the host: its CRC32 is the blocks' combined)
+                }
+            } else if (!rc && on_gpu && idx_has_crc && cmd == 't') {
                 // nlzm_hip_check: decoded into a buffer on the device, every block bounded by its index entry, and hashed there
                 const uint32_t k = (uint32_t)parts.size();
                 std::vector<uint64_t> blen(k), raw(k);
@@ -675,6 +731,7 @@ int main(int argc, char **argv)
                "\t-verify = (this build) c decodes what it wrote on the GPU, one workgroup per stream, compares it with the input\n"
                "\t          and removes the output if they differ\n"
                "\t-gpu = (this build) d / t decode on the GPU, all blocks of a container at once (without it they run on the host); h hashes there\n"
+               "\t-steps:K = (this build) d -gpu / t -gpu decode in steps of K frames per block; d writes every step's bytes as they come\n"
                "\t-crc = (this build) c hashes every block on the GPU and keeps the CRC32s in [output].idx (NLZMIDX 2), for one stream too;\n"
                "\t       d / t compare what they decode with an index that holds CRC32s and exit with status -4 if a block differs\n");
     }

@@ -41,13 +41,35 @@ static_assert((kRing & (kRing - 1)) == 0 && kRing >= 512, "the ring is a power o
 static_assert(kFlush + kMaxMatch + 16 <= kRing, "an op may not overwrite bytes of the ring that are not in memory yet");
 
 enum : int { kOk = 0, kErrCapacity = -4, kErrKernel = -5, kErrFormat = -7 };    // NLZM_HIP_E_CAPACITY, _KERNEL, _FORMAT
+enum : int { kPaused = 1 };                         // the stepping form only: stopped in front of a frame header, the state saved (no error)
+
+// ---- a decode at rest in front of a frame header (the stepping form, decode_role_steps) ---------------------------------------
+// What crosses a frame header: where the header lies, how much is decoded, the model and rep[4]; the rANS states and the bit word are a
+// frame's own, and the ring is a copy of output bytes that are in memory.  The record lies in device memory that the host library owns;
+// the role that pauses writes it, the role that resumes reads it.  The model: register r of lane l at model[r][l], one coalesced store a
+// register (entries fit 16 bits; kept as the dwords they are in the registers).
+constexpr uint32_t kModelRegs = 18;
+constexpr uint32_t kStateValid = 0x4E535431u;       // "NST1"
+struct StepState {
+    uint32_t model[kModelRegs][64];
+    unsigned long long pos, n;                      // stream offset of the next frame header (0: the stream's own header is still to be read), output bytes so far
+    unsigned long long syms, raw_ops, n_literal, n_dict, n_rep, ring_bytes, global_bytes, cycles, window_cycles, copy_cycles;     // the running counters
+    unsigned long long frames;                      // frames done
+    uint32_t rep[4];
+    uint32_t valid, pad_;                           // kStateValid while the decode is at rest; anything else: nothing to resume from
+};
+constexpr uint32_t kStateBytes = (uint32_t)sizeof(StepState);
 
 // one per stream (= per workgroup), in memory
 struct StreamArgs {
     const uint8_t *src; unsigned long long len;     // reads stay inside [src, src + len)
     uint8_t *dst; unsigned long long cap;           // writes stay inside [dst, dst + cap); dst == nullptr: size only, nothing is stored
     unsigned long long budget;                      // clock100() ticks the decode may take
-    uint32_t flags = 0;                             // kPrefix
+    uint32_t flags = 0;                             // kPrefix; the stepping form: kResume, kMore
+    // the stepping form (decode_role_steps) only; the one-shot role does not look at them
+    StepState *state = nullptr;                     // where a pause saves the decode and kResume finds it
+    uint32_t max_frames = 0;                        // pause after this many frames of this launch (0: no limit)
+    unsigned long long target = ~0ull;              // pause at the first frame boundary with out_len >= target
 };
 // kPrefix: reaching `cap` ends the decode SUCCESSFULLY (rc = kOk, out_len = cap): the literal that would land at dst + cap is not
 // written (not even decoded: the decode stops behind the op that brings n to cap), a match that runs over it is copied up to it
@@ -56,13 +78,23 @@ struct StreamArgs {
 // NOTHING behind the bytes it returns (a stream damaged there decodes as if it were whole).  The counters (syms, n_literal, ...)
 // count the ops up to and including the one that reached `cap`.  A stream that ends before `cap` reports its true, shorter out_len.
 // Without the flag a `cap` below the stream's length stays kErrCapacity.
-enum : uint32_t { kPrefix = 1u };
+//
+// The stepping form.  In front of every frame header -- where prefix mode makes its test, and nowhere else -- the decode PAUSES when
+// max_frames frames were decoded in this launch, when n >= target, or, with kMore only, when the header or the frame's nb + nr bytes do
+// not lie wholly inside [src, src + len): the stream's tail has not arrived (without kMore that stays kErrFormat, detail 3; with or
+// without it no read leaves [src, src + len)).  The terminator ends the decode (kOk) whatever the limits say.  A pause flushes the ring in
+// full, saves *state and reports rc = kPaused, out_len = n, why = the reason; kResume starts from *state instead of from the stream's four
+// header bytes.  The counters run on through the state: after the last step they are the one-shot decode's.  kPrefix does not combine
+// with a state (a decode cut in the middle of an op cannot be resumed): the host refuses it.
+enum : uint32_t { kPrefix = 1u, kResume = 2u, kMore = 4u };
+enum : uint32_t { kWhyNone = 0, kWhyFrames = 1, kWhyTarget = 2, kWhyInput = 3 };
 struct StreamResult {
     int rc; uint32_t detail;                        // detail: the host decoder's code for a format error (-1 .. -7, negated)
     unsigned long long out_len;                     // bytes decoded (an error: up to where it was noticed)
     unsigned long long syms, raw_ops, n_literal, n_dict, n_rep;     // the oracle's rans_syms, bit_ops, n_literal, n_dict, n_rep
     unsigned long long ring_bytes, global_bytes;    // match bytes served from the LDS ring / from memory
     unsigned long long cycles, window_cycles, copy_cycles;         // wave cycles: in all, waiting for input windows, copying and flushing
+    uint32_t why;                                   // written by the stepping form only: kWhy* of a pause, kWhyNone otherwise
 };
 
 // c += d for a counter: kept in VGPRs (every lane the same value) -- the role's wave-uniform state fills the scalar registers as it is
@@ -128,6 +160,15 @@ XW_FN void model_init(Model &m)
     for (int j = 0; j < 4; j++) { m.llo[j] = cdf_init(16); m.elo[j] = cdf_init(16); }
     for (int j = 0; j < 8; j++) m.slo[j] = cdf_init(8);
     for (uint32_t j = 0; j < 4; j++) m.rep[j] = j + 1;
+}
+// every model register with its index in StepState::model: constant indices after unrolling, never an indexed access to the registers
+template <class F> XW_FN void model_each(Model &m, F f)
+{
+    f(0u, m.misc); f(1u, m.shi);
+#pragma unroll
+    for (uint32_t j = 0; j < 4; j++) { f(2u + j, m.llo[j]); f(6u + j, m.elo[j]); }
+#pragma unroll
+    for (uint32_t j = 0; j < 8; j++) f(10u + j, m.slo[j]);
 }
 
 // ---- a frame ---------------------------------------------------------------------------------------------------------------------
@@ -220,7 +261,8 @@ XW_FN uint32_t match_min(uint32_t d) { return 2u + (d >= 256u) + (d >= 4096u) + 
 // stored in an earlier flush.  Every flush ends with xw::drain() -- s_waitcnt vmcnt(0) -- before anything else runs: the stores
 // have been acknowledged by the L2 when a later load of the same wave is issued, and the CU's vector L1 is write-through (a store
 // does not leave a stale line behind for the CU's own later loads).  One wave, program order, a completed store: no fence or
-// cache maintenance is needed, and no other wave or workgroup ever reads a stream's output while it is being decoded.
+// cache maintenance is needed, and no other wave or workgroup ever reads a stream's output while it is being decoded.  The bytes a
+// resumed decode preloads (and its saved state) were stored by an EARLIER launch: a kernel boundary makes them visible.
 struct Out {
     uint8_t *base;                                  // dst - a
     unsigned long long a, cap, n, fl;               // n: bytes decoded
@@ -244,6 +286,25 @@ XW_FN void flush(Out &O, bool all)
     if (t + l < vhi) O.base[t + l] = ring[(t + l) & (kRing - 1)];                  // (all: up to 15 bytes behind the last one)
     O.fl = vhi - O.a;
     xw::drain();
+    xw::wave_sync();
+}
+// flush's mirror image for a resumed decode: the last min(kRing, n) output bytes, which an earlier launch stored, from memory into the ring
+// (same alignment relation: 16 aligned bytes of memory are 16 aligned bytes of the ring).  Afterwards the ring holds what it would hold
+// had the decode never stopped, so copy() serves the same matches from it.  Reads stay inside [dst, dst + n).
+XW_FN void preload(Out &O)
+{
+    uint8_t *ring = xw::lds<Lds>()->ring;
+    const unsigned long long vhi = O.n + O.a, vlo = vhi - (O.n < kRing ? O.n : (unsigned long long)kRing);
+    if (vhi <= vlo) return;
+    const uint32_t l = xw::lane();
+    unsigned long long up = (vlo + 15) & ~15ull;
+    if (up > vhi) up = vhi;
+    if (vlo + l < up) ring[(vlo + l) & (kRing - 1)] = O.base[vlo + l];
+    const unsigned long long bend = vhi & ~15ull;
+    for (unsigned long long u = up + 16ull * l; u + 16 <= bend; u += 1024)
+        *(V16 *)(ring + (u & (kRing - 1))) = *(const V16 *)(O.base + u);
+    const unsigned long long t = bend > up ? bend : up;
+    if (t + l < vhi) ring[(t + l) & (kRing - 1)] = O.base[t + l];
     xw::wave_sync();
 }
 // lv bytes from dv back (dv <= n and n + lv <= cap checked by the caller)
@@ -290,7 +351,17 @@ XW_FN uint32_t ld_be32(const Src &S, unsigned long long pos)
     return (ld_u8(S, pos) << 24) | (ld_u8(S, pos + 1) << 16) | (ld_u8(S, pos + 2) << 8) | ld_u8(S, pos + 3);
 }
 
-XW_FN void decode_role(const StreamArgs &A, StreamResult *res)
+// (not XW_FN: the role is left to the optimiser's inliner, which takes it into its one caller AFTER the instantiation has been simplified.
+//  decode_kernel, -Rpass-analysis=kernel-resource-usage: 105 VGPRs, 106 SGPRs, scratch 0, LDS 65,536 either way; spilled SGPRs 49 this way,
+//  57 with the template forced in early, 54 as the plain forced-inline function it was before it became a template.  A compiler that
+//  decides otherwise shows at once: `make asmcheck-decode` holds "no calls" for both kernels, and
+//  tests/test_decode_steps_abi.py::test_one_shot_kernel_keeps_its_figures holds the figures above with the spills at 54 or fewer.)
+#ifdef NLZM_SIM
+#define NLZM_DEC_ROLE_FN inline
+#else
+#define NLZM_DEC_ROLE_FN __device__ inline
+#endif
+template <bool kSteps> NLZM_DEC_ROLE_FN void decode_role_t(const StreamArgs &A, StreamResult *res)
 {
     const unsigned long long t_begin = xw::tick(), c_begin = xw::clock100();
     Src S;
@@ -301,26 +372,57 @@ XW_FN void decode_role(const StreamArgs &A, StreamResult *res)
     Count C{ 0, 0, 0 };
     unsigned long long n_literal = 0, n_dict = 0, n_rep = 0, copy_cycles = 0;
     const unsigned long long len = A.len;
-    const bool prefix = (A.flags & kPrefix) && O.store;
+    const bool prefix = !kSteps && (A.flags & kPrefix) && O.store;
+    const bool more = kSteps && (A.flags & kMore);
+    unsigned long long frames = 0, cycles0 = 0;
+    uint32_t why = kWhyNone, frames_here = 0;
     int rc = kOk;
     uint32_t detail = 0;
 #define DEC_FAIL(code, why) { rc = (code); detail = (why); break; }
+#define DEC_PAUSE(reason) { why = (reason); break; }
     do {
-        if (len < 8) DEC_FAIL(kErrFormat, 1)
-        const uint32_t hb = (ld_u8(S, 0) << 8) + ld_u8(S, 1), fb = (ld_u8(S, 2) << 8) + ld_u8(S, 3);
-        if (hb < 10 || hb > 28 || fb < 12 || fb > 20) DEC_FAIL(kErrFormat, 2)
         Model m;
-        model_init(m);
-        unsigned long long pos = 4;
+        unsigned long long pos = 0;
+        if constexpr (kSteps) if (A.flags & kResume) {
+            const StepState *T = A.state;
+            if (xw::readfirst(T->valid) != kStateValid) DEC_FAIL(kErrKernel, 1)
+            pos = xw::readfirst64(T->pos); O.n = xw::readfirst64(T->n); O.fl = O.n; frames = xw::readfirst64(T->frames);
+            if (O.store && O.n > O.cap) DEC_FAIL(kErrCapacity, 0)
+            const uint32_t l = xw::lane();
+            model_each(m, [&](uint32_t r, uint32_t &v) { v = T->model[r][l]; });
+            m.rep[0] = xw::readfirst(T->rep[0]); m.rep[1] = xw::readfirst(T->rep[1]); m.rep[2] = xw::readfirst(T->rep[2]); m.rep[3] = xw::readfirst(T->rep[3]);
+            C.syms = T->syms; C.raw_ops = T->raw_ops; C.window_cycles = T->window_cycles;
+            n_literal = T->n_literal; n_dict = T->n_dict; n_rep = T->n_rep; copy_cycles = T->copy_cycles; cycles0 = T->cycles;
+            O.ring_bytes = T->ring_bytes; O.global_bytes = T->global_bytes;
+            if (O.store) preload(O);
+        }
+        bool head = true;                                   // the stream's four header bytes are still to be read
+        if constexpr (kSteps) {
+            head = pos == 0;                                // (a resumed decode: only when it paused before they had arrived)
+            if (head && len < 8 && more) { model_init(m); why = kWhyInput; head = false; }     // (saved below like every pause; the resume starts over)
+        }
+        if (head) {
+            if (len < 8) DEC_FAIL(kErrFormat, 1)
+            const uint32_t hb = (ld_u8(S, 0) << 8) + ld_u8(S, 1), fb = (ld_u8(S, 2) << 8) + ld_u8(S, 3);
+            if (hb < 10 || hb > 28 || fb < 12 || fb > 20) DEC_FAIL(kErrFormat, 2)
+            model_init(m);
+            pos = 4;
+        }
         uint32_t ops_seen = 0;
         for (;;) {
+            if constexpr (kSteps) { if (why) break; }
             if (prefix && O.n >= O.cap) break;              // the prefix is whole: not a byte of what follows is looked at, no frame header either
-            if (pos + 4 > len) DEC_FAIL(kErrFormat, 3)
+            // THE pause test of the stepping form: a limit that is reached (it gives way to the terminator only), then input that is not there yet
+            uint32_t lim = kWhyNone;
+            if constexpr (kSteps) lim = A.max_frames && frames_here >= A.max_frames ? kWhyFrames : O.n >= A.target ? kWhyTarget : kWhyNone;
+            if (pos + 4 > len) { if constexpr (kSteps) { if (lim) DEC_PAUSE(lim) if (more) DEC_PAUSE(kWhyInput) } DEC_FAIL(kErrFormat, 3) }
             Frame F;
             F.num_ops = ld_be32(S, pos);
             if (!F.num_ops) break;
-            if (pos + 12 > len) DEC_FAIL(kErrFormat, 3)
+            if constexpr (kSteps) { if (lim) DEC_PAUSE(lim) }
+            if (pos + 12 > len) { if constexpr (kSteps) { if (more) DEC_PAUSE(kWhyInput) } DEC_FAIL(kErrFormat, 3) }
             const uint32_t nb = ld_be32(S, pos + 4), nr = ld_be32(S, pos + 8);
+            if constexpr (kSteps) { if (more && nb >= 12 && nr >= 16 && pos + (unsigned long long)nb + nr > len) DEC_PAUSE(kWhyInput) }
             if (nb < 12 || nr < 16 || pos + (unsigned long long)nb + nr > len) DEC_FAIL(kErrFormat, 3)
             F.bp = pos + 12; F.rp = pos + nb; F.end = pos + nb + nr;
             F.word = 0; F.word_bits = 0; F.bad = false;
@@ -399,17 +501,39 @@ XW_FN void decode_role(const StreamArgs &A, StreamResult *res)
             if (rc) break;
             if (F.bad) DEC_FAIL(kErrFormat, 7)
             pos += (unsigned long long)nb + nr;
+            if constexpr (kSteps) { frames++; frames_here++; }
         }
         if (!rc && O.store) flush(O, true);
+        if constexpr (kSteps) if (!rc && why) {             // at rest in front of the header at `pos`: everything decoded is in memory
+            StepState *T = A.state;
+            const uint32_t l = xw::lane();
+            model_each(m, [&](uint32_t r, uint32_t &v) { T->model[r][l] = v; });
+            if (l == 0) {
+                T->pos = pos; T->n = O.n; T->frames = frames;
+                T->syms = C.syms; T->raw_ops = C.raw_ops; T->n_literal = n_literal; T->n_dict = n_dict; T->n_rep = n_rep;
+                T->ring_bytes = O.ring_bytes; T->global_bytes = O.global_bytes;
+                T->cycles = cycles0 + (xw::tick() - t_begin); T->window_cycles = C.window_cycles; T->copy_cycles = copy_cycles;
+                T->rep[0] = m.rep[0]; T->rep[1] = m.rep[1]; T->rep[2] = m.rep[2]; T->rep[3] = m.rep[3];
+            }
+            rc = kPaused;
+        }
     } while (0);
 #undef DEC_FAIL
+#undef DEC_PAUSE
+    if constexpr (kSteps) if (xw::lane() == 0) {
+        A.state->valid = rc == kPaused ? kStateValid : 0u;  // (a decode that has ended, either way, leaves nothing to resume from)
+        res->why = rc == kPaused ? why : kWhyNone;
+    }
     if (xw::lane() == 0) {
         res->rc = rc; res->detail = detail; res->out_len = O.n;
         res->syms = C.syms; res->raw_ops = C.raw_ops; res->n_literal = n_literal; res->n_dict = n_dict; res->n_rep = n_rep;
         res->ring_bytes = O.ring_bytes; res->global_bytes = O.global_bytes;
-        res->cycles = xw::tick() - t_begin; res->window_cycles = C.window_cycles; res->copy_cycles = copy_cycles;
+        res->cycles = cycles0 + (xw::tick() - t_begin); res->window_cycles = C.window_cycles; res->copy_cycles = copy_cycles;
     }
 }
+// the one-shot decode, and the stepping form: the same role with the pause test, the saved state and the ring reload compiled in
+XW_FN void decode_role(const StreamArgs &A, StreamResult *res) { decode_role_t<false>(A, res); }
+XW_FN void decode_role_steps(const StreamArgs &A, StreamResult *res) { decode_role_t<true>(A, res); }
 
 // ---- the split of a container -------------------------------------------------------------------------------------------------------
 // stream_length (nlzm_host_decode.h) for nblocks streams back to back: ONE lane follows the sizes the frame headers carry (no cross-lane

@@ -1,4 +1,5 @@
-// nlzm_decode.hip -- the decoder's kernels for gfx950: the decoder role (nlzm_decode.h) one workgroup of one wave per stream, the hop
+// nlzm_decode.hip -- the decoder's kernels for gfx950: the decoder role (nlzm_decode.h) one workgroup of one wave per stream, one-shot
+// (decode_kernel) and in steps that stop at a frame boundary and resume (decode_steps_kernel), the hop
 // over the frame headers that splits a back-to-back container, and the compare of verify.  Nothing here is shared with the compress
 // pipeline (nlzm_kernels.hip); the host side is nlzm_hip_decode.cpp.
 #include <hip/hip_runtime.h>
@@ -24,6 +25,17 @@ __global__ __launch_bounds__(64) void decode_kernel(const dec::StreamArgs *__res
     a.src = NLZM_G(const uint8_t, a.src);
     a.dst = NLZM_G(uint8_t, a.dst);
     dec::decode_role(a, res + blockIdx.x);
+}
+
+// The stepping form of the same role (dec::decode_role_steps): workgroup b takes stream b up to its next pause or its end.  A kernel of its
+// own, so that decode_kernel stays the code it was.
+__global__ __launch_bounds__(64) void decode_steps_kernel(const dec::StreamArgs *__restrict__ args, dec::StreamResult *__restrict__ res)
+{
+    dec::StreamArgs a = args[blockIdx.x];
+    a.src = NLZM_G(const uint8_t, a.src);
+    a.dst = NLZM_G(uint8_t, a.dst);
+    a.state = NLZM_G(dec::StepState, a.state);
+    dec::decode_role_steps(a, res + blockIdx.x);
 }
 
 // the split of a container in device memory (dec::split_walk, nlzm_decode.h): one lane follows the sizes the frame headers carry
@@ -61,6 +73,10 @@ __global__ __launch_bounds__(256) void compare_kernel(const uint8_t *__restrict_
 void launch_decode(const void *d_args, void *d_res, uint32_t nstreams, hipStream_t st)
 {
     hipLaunchKernelGGL(decode_kernel, dim3(nstreams), dim3(64), 0, st, (const dec::StreamArgs *)d_args, (dec::StreamResult *)d_res);
+}
+void launch_decode_steps(const void *d_args, void *d_res, uint32_t nstreams, hipStream_t st)
+{
+    hipLaunchKernelGGL(decode_steps_kernel, dim3(nstreams), dim3(64), 0, st, (const dec::StreamArgs *)d_args, (dec::StreamResult *)d_res);
 }
 void launch_split(const void *d_src, unsigned long long len, uint32_t nblocks, unsigned long long *d_block_len, uint32_t *d_bad, hipStream_t st)
 {

@@ -18,6 +18,8 @@ struct Last {
     dec::StreamResult sum{};
     unsigned long long max_cycles = 0, max_stream = 0, streams = 0, passes = 0;
     double ms = 0;                                  // device time of all passes of the last call
+    unsigned long long steps = 0;                   // launches of the open (or last) decode set
+    double step_ms = 0;                             // device time of its last step
 };
 PerDevice<Last> g_last;
 
@@ -48,8 +50,8 @@ dec::StreamArgs decode_stream_args(const uint8_t *d_stream, uint64_t len, uint8_
     return dec::StreamArgs{ d_stream, len, d_dst, cap, (60ull + len / 1000000ull) * 100000000ull };
 }
 
-// one launch of the streams in `args` (a destination pointer, a bound and the flags per stream); res: what each reported
-int decode_run_streams(hipStream_t st, const std::vector<dec::StreamArgs> &args, std::vector<dec::StreamResult> &res)
+// one timed launch of the streams in `args`, by the one-shot kernel or by the stepping one; the call's device time and pass count go on
+static int launch_streams(hipStream_t st, const std::vector<dec::StreamArgs> &args, std::vector<dec::StreamResult> &res, bool steps, float *ms)
 {
     const size_t k = args.size();
     DevBuf da, dr;
@@ -57,18 +59,27 @@ int decode_run_streams(hipStream_t st, const std::vector<dec::StreamArgs> &args,
     if (!rc) rc = dr.alloc(k * sizeof(dec::StreamResult));
     if (rc) return rc;
     res.assign(k, dec::StreamResult{});
-    float ms = 0;
-    rc = timed_launch(st, "decode", &ms,
+    rc = timed_launch(st, steps ? "decode step" : "decode", ms,
         [&] {
             const hipError_t e = hipMemcpyAsync(da.p, args.data(), k * sizeof(dec::StreamArgs), hipMemcpyHostToDevice, st);
             return e != hipSuccess ? e : hipMemsetAsync(dr.p, 0xFF, k * sizeof(dec::StreamResult), st);        // (a workgroup that never ran reports rc = -1)
         },
-        [&] { launch_decode(da.p, dr.p, (uint32_t)k, st); },
+        [&] { if (steps) launch_decode_steps(da.p, dr.p, (uint32_t)k, st); else launch_decode(da.p, dr.p, (uint32_t)k, st); },
         [&] { return hipMemcpyAsync(res.data(), dr.p, k * sizeof(dec::StreamResult), hipMemcpyDeviceToHost, st); });
     if (rc) return rc;
     Last &L = g_last.here();
-    L.ms += ms;
+    L.ms += *ms;
     L.passes++;
+    return 0;
+}
+
+// one launch of the streams in `args` (a destination pointer, a bound and the flags per stream); res: what each reported
+int decode_run_streams(hipStream_t st, const std::vector<dec::StreamArgs> &args, std::vector<dec::StreamResult> &res)
+{
+    const size_t k = args.size();
+    float ms = 0;
+    if (const int rc = launch_streams(st, args, res, false, &ms)) return rc;
+    Last &L = g_last.here();
     L.sum = dec::StreamResult{};
     L.max_cycles = 0; L.max_stream = 0;
     L.streams = k;
@@ -150,6 +161,9 @@ int decode_counter(const char *key, uint64_t *value)
     if (!strcmp(key, "decode_passes")) { *value = L.passes; return 0; }
     if (!strcmp(key, "decode_ms")) { *value = (uint64_t)(L.ms + 0.5); return 0; }
     if (!strcmp(key, "decode_us")) { *value = (uint64_t)(L.ms * 1000.0 + 0.5); return 0; }
+    if (!strcmp(key, "decode_steps")) { *value = L.steps; return 0; }
+    if (!strcmp(key, "decode_step_us")) { *value = (uint64_t)(L.step_ms * 1000.0 + 0.5); return 0; }
+    if (!strcmp(key, "decode_state_bytes")) { *value = dec::kStateBytes; return 0; }      // (needs no device)
     return fail(NLZM_HIP_E_ARG, "unknown counter %s", key);
 }
 
@@ -361,5 +375,223 @@ int nlzm_hip_check(const uint8_t *src, uint64_t src_len, uint32_t nblocks, const
     HIPCHK(hipStreamSynchronize(st));
     return nlzm_hip_check_dev(ds.p, src_len, nblocks, block_len, raw_len, crc, first_bad, crc_out);
 }
+
+}  // extern "C"
+
+// ---- decoding in steps: one open decode set per device state (the idiom of nlzm_hip_blocks_begin / _step / _finish / _abandon) ----------------
+namespace {
+
+struct StepSet {
+    bool open = false, more = false, bounded = false, cut_off = false, extended_flat = false;
+    const uint8_t *d_src = nullptr;
+    uint8_t *d_dst = nullptr;                       // nullptr: size-only stepping
+    void *own_src = nullptr, *own_dst = nullptr;    // the host form's: the uploaded container, the library's output buffer
+    dec::StepState *states = nullptr;
+    uint32_t nblocks = 0;
+    std::vector<uint64_t> off, len, bound, at, done;        // per block: stream offset and length, bound on its output, its offset in the output, bytes decoded
+    std::vector<uint8_t> fin, started;
+    std::vector<dec::StreamResult> tot;             // every block's running totals (what its last launch reported)
+    uint64_t total = 0;                             // bounded: the sum of the blocks' lengths
+};
+PerDevice<StepSet> g_steps;
+
+void steps_close(StepSet &S)
+{
+    if (S.states) (void)hipFree(S.states);
+    if (S.own_src) (void)hipFree(S.own_src);
+    if (S.own_dst) (void)hipFree(S.own_dst);
+    S = StepSet{};
+}
+
+// binds what begin found: the split, the bounds, one state record per block.  Decodes nothing.
+int steps_open(StepSet &S, hipStream_t st, const std::vector<uint64_t> &off, const std::vector<uint64_t> &len, const uint64_t *raw_len, uint64_t dst_cap)
+{
+    const uint32_t k = S.nblocks;
+    S.off = off; S.len = len;
+    S.bound.assign(k, 0); S.at.assign(k, 0); S.done.assign(k, 0); S.fin.assign(k, 0); S.started.assign(k, 0); S.tot.assign(k, dec::StreamResult{});
+    S.bounded = raw_len != nullptr;
+    uint64_t total = 0;
+    for (uint32_t i = 0; i < k; i++) {
+        S.at[i] = total;
+        S.bound[i] = raw_len ? raw_len[i] : (S.d_dst ? dst_cap : ~0ull);
+        if (raw_len) { if (raw_len[i] > ~0ull - total) return fail(NLZM_HIP_E_ARG, "the blocks' lengths do not fit 64 bits"); total += raw_len[i]; }
+    }
+    S.total = total;
+    if (S.d_dst && raw_len && total > dst_cap) return fail(NLZM_HIP_E_CAPACITY, "the blocks decode to %llu bytes, dst_cap %llu", (unsigned long long)total, (unsigned long long)dst_cap);
+    HIPCHK(hipMalloc((void **)&S.states, (size_t)k * sizeof(dec::StepState)));
+    HIPCHK(hipMemsetAsync(S.states, 0, (size_t)k * sizeof(dec::StepState), st));
+    HIPCHK(hipStreamSynchronize(st));
+    Last &L = g_last.here();
+    L.steps = 0; L.step_ms = 0;
+    S.open = true;
+    return 0;
+}
+
+}  // namespace
+
+extern "C" {
+
+int nlzm_hip_decode_begin_dev(const void *d_src, uint64_t src_len, uint32_t nblocks, const uint64_t *block_len, const uint64_t *raw_len, void *d_dst, uint64_t dst_cap, uint32_t flags)
+{
+    hipStream_t st;
+    if (const int rc = host_stream(&st)) return rc;
+    StepSet &S = g_steps.here();
+    steps_close(S);                                 // a second begin closes the set before it
+    if (!d_src || !nblocks || nblocks > 65536) return fail(NLZM_HIP_E_ARG, "null argument, or nblocks outside 1 .. 65536");
+    if (flags & ~(uint32_t)NLZM_HIP_DECODE_MORE) return fail(NLZM_HIP_E_ARG, "unknown flags %u (a decode that is cut in the middle of an op, as a prefix read is, cannot be resumed)", flags);
+    if ((flags & NLZM_HIP_DECODE_MORE) && nblocks != 1) return fail(NLZM_HIP_E_ARG, "NLZM_HIP_DECODE_MORE is for one stream");
+    if (!raw_len && nblocks != 1) return fail(NLZM_HIP_E_ARG, "raw_len may be NULL for one stream only");
+    decode_begin_call();
+    std::vector<uint64_t> off, len;
+    if (flags & NLZM_HIP_DECODE_MORE) { off.assign(1, 0); len.assign(1, src_len); }       // (what has arrived so far: nothing to hop over yet)
+    else if (const int rc = decode_split(st, d_src, src_len, nblocks, block_len, off, len)) return rc;
+    S.d_src = (const uint8_t *)d_src; S.d_dst = (uint8_t *)d_dst; S.nblocks = nblocks; S.more = (flags & NLZM_HIP_DECODE_MORE) != 0;
+    const int rc = steps_open(S, st, off, len, raw_len, dst_cap);
+    if (rc) steps_close(S);
+    return rc;
+}
+
+int nlzm_hip_decode_begin(const uint8_t *src, uint64_t src_len, uint32_t nblocks, const uint64_t *block_len, const uint64_t *raw_len, uint32_t flags)
+{
+    hipStream_t st;
+    if (const int rc = host_stream(&st)) return rc;
+    StepSet &S = g_steps.here();
+    steps_close(S);
+    if (!src || !nblocks || nblocks > 65536) return fail(NLZM_HIP_E_ARG, "null argument, or nblocks outside 1 .. 65536");
+    if (flags) return fail(NLZM_HIP_E_ARG, "flags %u: NLZM_HIP_DECODE_MORE is for nlzm_hip_decode_begin_dev (a decode cut in the middle of an op cannot be resumed)", flags);
+    decode_begin_call();
+    std::vector<uint64_t> off, len, raw;
+    int rc = decode_split_host(src, src_len, nblocks, block_len, off, len);
+    if (rc) return rc;
+    HIPCHK(hipMalloc(&S.own_src, src_len ? src_len : 16));
+    rc = [&]() -> int {
+        HIPCHK(hipMemcpyAsync(S.own_src, src, src_len, hipMemcpyHostToDevice, st));
+        HIPCHK(hipStreamSynchronize(st));
+        if (raw_len) raw.assign(raw_len, raw_len + nblocks);
+        else if (const int r = decode_sizes(st, (const uint8_t *)S.own_src, off, len, raw)) return r;      // the existing size pass
+        uint64_t total = 0;
+        for (uint32_t i = 0; i < nblocks; i++) { if (raw[i] > ~0ull - total) return fail(NLZM_HIP_E_ARG, "the blocks' lengths do not fit 64 bits"); total += raw[i]; }
+        HIPCHK(hipMalloc(&S.own_dst, total ? total : 16));
+        S.d_src = (const uint8_t *)S.own_src; S.d_dst = (uint8_t *)S.own_dst; S.nblocks = nblocks; S.more = false;
+        return steps_open(S, st, off, len, raw.data(), total);
+    }();
+    if (rc) steps_close(S);
+    return rc;
+}
+
+int nlzm_hip_decode_step(uint32_t max_frames, const uint64_t *target, uint64_t *done, int *finished, double *device_ms)
+{
+    hipStream_t st;
+    if (const int rc = host_stream(&st)) return rc;
+    StepSet &S = g_steps.here();
+    if (!S.open) return fail(NLZM_HIP_E_ARG, "no decode set is open");
+    if (!finished) return fail(NLZM_HIP_E_ARG, "null argument");
+    decode_begin_call();
+    Last &L = g_last.here();
+    L.step_ms = 0;
+    const uint32_t k = S.nblocks;
+    std::vector<dec::StreamArgs> args;
+    std::vector<uint32_t> who;
+    for (uint32_t i = 0; i < k; i++) {
+        if (S.fin[i] || (target && S.done[i] >= target[i])) continue;       // finished, or at its target already: not launched
+        dec::StreamArgs a = decode_stream_args(S.d_src + S.off[i], S.len[i], S.d_dst ? S.d_dst + S.at[i] : nullptr, S.bound[i]);
+        a.flags = (S.started[i] ? dec::kResume : 0u) | (S.more ? dec::kMore : 0u);
+        a.state = S.states + i; a.max_frames = max_frames; a.target = target ? target[i] : ~0ull;
+        args.push_back(a); who.push_back(i);
+    }
+    if (!args.empty()) {
+        std::vector<dec::StreamResult> res;
+        float ms = 0;
+        int rc = launch_streams(st, args, res, true, &ms);
+        for (size_t j = 0; !rc && j < who.size(); j++) {
+            const uint32_t i = who[j];
+            const dec::StreamResult &r = res[j];
+            S.tot[i] = r; S.done[i] = r.out_len; S.started[i] = 1;
+            if (r.rc == dec::kErrFormat) rc = fail(NLZM_HIP_E_FORMAT, "block %u of %u is not a well-formed NLZM stream (check %u failed after %llu output bytes)", i + 1, k, r.detail, r.out_len);
+            else if (r.rc == dec::kErrCapacity) rc = fail(NLZM_HIP_E_CAPACITY, "block %u of %u decodes to more than the %llu bytes there is room for", i + 1, k, (unsigned long long)S.bound[i]);
+            else if (r.rc != dec::kOk && r.rc != dec::kPaused) rc = fail(NLZM_HIP_E_KERNEL, "decode step kernel: block %u of %u ended with code %d after %llu output bytes", i + 1, k, r.rc, r.out_len);
+            else if (r.rc == dec::kOk) {
+                S.fin[i] = 1;
+                if (S.bounded && r.out_len > S.bound[i]) rc = fail(NLZM_HIP_E_CAPACITY, "block %u decodes to %llu bytes, more than the %llu it was said to hold", i + 1, r.out_len, (unsigned long long)S.bound[i]);
+                else if (S.bounded && r.out_len != S.bound[i]) rc = fail(NLZM_HIP_E_FORMAT, "block %u decodes to %llu bytes, not the %llu it was said to hold", i + 1, r.out_len, (unsigned long long)S.bound[i]);
+            } else if (S.more && r.why == dec::kWhyInput && S.extended_flat) S.cut_off = true;      // the caller said "no more" and the stream still wants some
+        }
+        if (rc) { steps_close(S); return rc; }      // a failing step closes the set (block mode's rule)
+        L.steps++;
+        L.step_ms = ms;
+    }
+    // the set's totals so far
+    L.sum = dec::StreamResult{};
+    L.max_cycles = 0; L.max_stream = 0; L.streams = k;
+    bool all = true;
+    for (uint32_t i = 0; i < k; i++) {
+        const dec::StreamResult &r = S.tot[i];
+        L.sum.syms += r.syms; L.sum.raw_ops += r.raw_ops; L.sum.n_literal += r.n_literal; L.sum.n_dict += r.n_dict; L.sum.n_rep += r.n_rep;
+        L.sum.ring_bytes += r.ring_bytes; L.sum.global_bytes += r.global_bytes; L.sum.out_len += S.done[i];
+        L.sum.cycles += r.cycles; L.sum.window_cycles += r.window_cycles; L.sum.copy_cycles += r.copy_cycles;
+        if (r.cycles > L.max_cycles) { L.max_cycles = r.cycles; L.max_stream = i; }
+        if (done) done[i] = S.done[i];
+        all = all && S.fin[i];
+    }
+    *finished = all ? 1 : 0;
+    if (device_ms) *device_ms = L.step_ms;
+    return 0;
+}
+
+int nlzm_hip_decode_extend_dev(uint64_t src_len_now)
+{
+    hipStream_t st;
+    if (const int rc = host_stream(&st)) return rc;
+    StepSet &S = g_steps.here();
+    if (!S.open || !S.more) return fail(NLZM_HIP_E_ARG, "no decode set with NLZM_HIP_DECODE_MORE is open");
+    if (src_len_now < S.len[0]) return fail(NLZM_HIP_E_ARG, "the stream cannot shrink (%llu bytes were there, now %llu)", (unsigned long long)S.len[0], (unsigned long long)src_len_now);
+    S.extended_flat = src_len_now == S.len[0];      // an extend without growth: the caller's "that was all"
+    if (!S.extended_flat) S.cut_off = false;        // (more has come after all: a step that paused for want of it no longer says "cut off")
+    S.len[0] = src_len_now;
+    return 0;
+}
+
+int nlzm_hip_decode_fetch(uint64_t off, uint64_t len, uint8_t *dst)
+{
+    hipStream_t st;
+    if (const int rc = host_stream(&st)) return rc;
+    StepSet &S = g_steps.here();
+    if (!S.open) return fail(NLZM_HIP_E_ARG, "no decode set is open");
+    if (!S.d_dst) return fail(NLZM_HIP_E_ARG, "the open decode set only sizes: it stores nothing");
+    if (!dst && len) return fail(NLZM_HIP_E_ARG, "null argument");
+    const uint64_t total = S.bounded ? S.total : S.done[0];
+    if (off > total || len > total - off) return fail(NLZM_HIP_E_ARG, "the range (offset %llu, %llu bytes) runs over the %llu bytes there are", (unsigned long long)off, (unsigned long long)len, (unsigned long long)total);
+    if (!len) return 0;
+    for (uint32_t i = 0; i < S.nblocks; i++) {      // every block the range intersects must have decoded up to where the range ends in it
+        const uint64_t lo = S.at[i], hi = S.bounded ? lo + S.bound[i] : total;
+        if (hi <= off || lo >= off + len) continue;
+        const uint64_t need = (off + len < hi ? off + len : hi) - lo;
+        if (S.done[i] < need) return fail(NLZM_HIP_E_ARG, "block %u has decoded %llu bytes, the range needs %llu of it", i + 1, (unsigned long long)S.done[i], (unsigned long long)need);
+    }
+    HIPCHK(hipMemcpyAsync(dst, S.d_dst + off, len, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    return 0;
+}
+
+int nlzm_hip_decode_finish(uint64_t *raw_len_out, uint64_t *dst_len)
+{
+    hipStream_t st;
+    if (const int rc = host_stream(&st)) return rc;
+    StepSet &S = g_steps.here();
+    if (!S.open) return fail(NLZM_HIP_E_ARG, "no decode set is open");
+    bool all = true;
+    for (uint32_t i = 0; i < S.nblocks; i++) all = all && S.fin[i];
+    if (!all) {
+        if (S.cut_off) { steps_close(S); return fail(NLZM_HIP_E_FORMAT, "the stream is cut off: it pauses for input that the caller says will not come"); }
+        return fail(NLZM_HIP_E_ARG, "the decode set has not reached its end (the set stays open)");
+    }
+    uint64_t total = 0;
+    for (uint32_t i = 0; i < S.nblocks; i++) { if (raw_len_out) raw_len_out[i] = S.done[i]; total += S.done[i]; }
+    if (dst_len) *dst_len = total;
+    steps_close(S);
+    return 0;
+}
+
+void nlzm_hip_decode_abandon(void) { steps_close(g_steps.here()); }
 
 }  // extern "C"

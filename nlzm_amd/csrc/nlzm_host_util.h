@@ -25,6 +25,7 @@ int host_error(int code, const char *text);
 int host_stream(hipStream_t *st);
 // nlzm_decode.hip, nlzm_crc.hip, nlzm_range.hip
 void launch_decode(const void *d_args, void *d_res, uint32_t nstreams, hipStream_t st);
+void launch_decode_steps(const void *d_args, void *d_res, uint32_t nstreams, hipStream_t st);      // the stepping form: args carry state, max_frames, target
 void launch_split(const void *d_src, unsigned long long len, uint32_t nblocks, unsigned long long *d_block_len, uint32_t *d_bad, hipStream_t st);
 void launch_compare(const void *d_a, const void *d_b, unsigned long long n, unsigned long long *d_first, hipStream_t st);
 void launch_crc(const crc::Args &a, uint32_t max_blocks, hipStream_t st);
