@@ -105,7 +105,7 @@ int nlzm_hip_stream_finish(uint64_t *dst_len);
 int nlzm_hip_get_stats(nlzm_hip_stats *out);
 int nlzm_hip_get_timing(nlzm_hip_timing *out);
 /* Diagnostic counters of the pipeline stages for the last stream (what "stage_report" prints, by name; also "block_pool_bytes", "block_redo_streams",
- * "gpu_max_hw_queues_effective"): cycles are summed over the
+ * "container_sets", "gpu_max_hw_queues_effective"): cycles are summed over the
  * stream's launches, e.g. "parser_total_cycles", "parser_wait_cycles", "parser_pass_cycles", "parser_passes", "parser_blocks",
  * "finder_total_cycles", "finder_wait_cycles", "finder_bt_wait_cycles", "table_total_cycles", "table_wait_cycles", "helper_jobs",
  * "helper_taken", "helper_taken_nodes", "helper_wait_cycles", "worker_call_cycles", "worker_call_tests", "worker_calls",
@@ -172,11 +172,26 @@ int nlzm_hip_blocks_begin(const void *d_src, uint64_t n, uint32_t nblocks, uint3
 int nlzm_hip_blocks_step(uint32_t max_chunks_per_block, uint64_t *in_done_total, int *finished, double *device_ms);
 int nlzm_hip_blocks_finish(void *d_dst, uint64_t dst_cap, uint64_t *block_len, uint64_t *dst_len);
 void nlzm_hip_blocks_abandon(void);
-/* one-shot form */
+/* One-shot form.  nblocks: 1 .. 65536.  Up to the device's capacity (what nlzm_hip_blocks_begin takes: 64 on an MI355X) this is begin, one step to
+ * the end and finish -- ONE set, 33 to 64 blocks included.  More blocks than that are the same ceil(n / nblocks) partition, compressed in
+ * ceil(nblocks / "container_set_blocks") sets one after another, as equal as they can be (65 blocks by 32: 22 + 22 + 21): every set is such a block set
+ * with the partition fixed, its streams go straight to their place in d_dst and block_len, and block i holds the bytes of the reference run on its byte
+ * range whatever set it falls into (a block wholly behind the input's end: the empty stream; a whole set may consist of those).  The sets neither
+ * overlap nor change a kernel; the block set's one allocation is used again from set to set (with "keep_block_pool" 0 too: it is then released when the call
+ * ends, and "block_pool_bytes" reads 0 as after any set).  A set that fails ends the call with
+ * its error and nothing open.  Afterwards nlzm_hip_get_stats is the sum over all sets, "block_redo_streams" counts over all of them,
+ * "block_pool_bytes" is the largest set's and "container_sets" says how many sets ran (1: the blocks fitted one launch).  d_dst needs room for
+ * nlzm_hip_compress_blocks_bound(n, nblocks) at most.  (nlzm_hip_get_timing is the single stream's: no block set, and no container, writes it.)  The stepping form above keeps its limit: there is none for containers. */
 int nlzm_hip_compress_blocks_dev(const void *d_src, uint64_t n, uint32_t nblocks, uint32_t hist_bits_req,
                                  void *d_dst, uint64_t dst_cap, uint64_t *block_len, uint64_t *dst_len);
 
-/* same, host buffers */
+/* Room the streams of nblocks blocks of n bytes take at most, for d_dst / dst of the one-shot forms: up to 64 blocks nlzm_hip_compress_bound(n) and
+ * a margin of 128 KiB a stream, as ever; above that the sum of nlzm_hip_compress_bound(block's length) over the blocks -- a guaranteed bound for a
+ * container compressed in sets (about 148 KB a block: 9.7 GB at 65,536 blocks, most of it never touched).  Needs no device.  0 when nblocks is 0 or
+ * above 65536. */
+uint64_t nlzm_hip_compress_blocks_bound(uint64_t n, uint32_t nblocks);
+
+/* same, host buffers (the device output is sized by nlzm_hip_compress_blocks_bound) */
 int nlzm_hip_compress_blocks(const uint8_t *src, uint64_t n, uint32_t nblocks, uint32_t hist_bits_req,
                              uint8_t *dst, uint64_t dst_cap, uint64_t *block_len, uint64_t *dst_len);
 
@@ -223,7 +238,13 @@ void nlzm_hip_block_placement(uint32_t nstreams, uint32_t blocks_per_stream, uin
  * oracle's rans_syms, bit_ops, n_literal, n_dict, n_rep), "decode_out_bytes", "decode_ring_bytes" / "decode_global_bytes" (match bytes served
  * from the LDS ring / from memory), "decode_cycles", "decode_window_cycles", "decode_copy_cycles" (wave cycles summed over the streams: in all,
  * waiting for input windows, copying and flushing), "decode_max_stream_cycles" and "decode_slowest_stream" (the stream with the most cycles and its index), "decode_streams", "decode_passes", "decode_ms" / "decode_us"
- * (device time of the call's decode launches; nlzm_hip_timing stays the compress path's). */
+ * (device time of the call's decode launches; nlzm_hip_timing stays the compress path's), "decode_ring_size" (the LDS ring of the kernel the call's last
+ * decode launch ran).
+ * Two one-shot kernels run the same role: decode_kernel with a 64 KiB ring -- a CU's LDS holds two of its one-wave workgroups, 2 x CUs streams are at work
+ * at once, each wave with a SIMD to itself -- and decode_small_kernel with a 16 KiB ring, ten workgroups to a CU, whose waves fill each other's issue gaps;
+ * matches that reach further back than the ring are served from memory by either.  Option "decode_ring" picks: 0 (default) by the launch -- more
+ * streams than 2 x CUs run the small kernel, every other launch the big one --, 65536 / 16384 force one.  It holds for every one-shot decode launch:
+ * nlzm_hip_decompress*, nlzm_hip_verify*, nlzm_hip_check*, nlzm_hip_read_ranges* (prefix mode included).  The stepping form always has 64 KiB. */
 
 /* d_dst == NULL: size query, *dst_len = uncompressed length (the format stores none: the stream is decoded without storing).
  * dst_cap too small: NLZM_HIP_E_CAPACITY, nothing written at or beyond d_dst + dst_cap. */
@@ -361,7 +382,10 @@ int nlzm_hip_read_ranges(const uint8_t *src, uint64_t src_len, uint32_t nblocks,
  * test only: "test_fail_launch" (default -1) / "test_fail_stream": the finder stage of that launch of that stream of a block set (of the single stream)
  * raises an error at once; "block_ext_blocks" (default -1: by the launch's size): extension blocks of a block-set stream's pair-list arena;
  * "stage_report" (1: the stages' cycle accounting of
- * every finished stream, and of a block set per stream, on stderr).  There are no environment knobs.
+ * every finished stream, and of a block set per stream, on stderr; a container compressed in sets reports set by set);
+ * "container_set_blocks" (default 32, 1 .. the device's capacity -- 64 on an MI355X: blocks per set of a container that nlzm_hip_compress_blocks* compresses
+ * in sets); "decode_ring" (0, 65536 or 16384: which one-shot decode kernel runs, see the decoding section; read by every decode launch).
+ * There are no environment knobs.
  * None of them changes a byte of the output.  The options are read when a stream or a block set is opened
  * (nlzm_hip_stream_begin, nlzm_hip_blocks_begin, nlzm_hip_feed_begin, the one-call entries): what is open keeps what it was opened with.
  * nlzm_hip_compress_blocks_multi is EXPERIMENTAL until a run on more than one device has been recorded (it has only been run with one). */

@@ -28,7 +28,7 @@ ABI_SYMBOLS = [
     "nlzm_hip_stream_step", "nlzm_hip_stream_finish", "nlzm_hip_get_stats", "nlzm_hip_get_timing",
     "nlzm_hip_rans_frames", "nlzm_hip_find_matches", "nlzm_hip_parse_emit", "nlzm_hip_set_option",
     "nlzm_hip_blocks_begin", "nlzm_hip_blocks_step", "nlzm_hip_blocks_finish", "nlzm_hip_blocks_abandon",
-    "nlzm_hip_compress_blocks_dev", "nlzm_hip_compress_blocks", "nlzm_hip_compress_blocks_multi",
+    "nlzm_hip_compress_blocks_dev", "nlzm_hip_compress_blocks", "nlzm_hip_compress_blocks_multi", "nlzm_hip_compress_blocks_bound",
     "nlzm_hip_feed_begin", "nlzm_hip_feed", "nlzm_hip_feed_output", "nlzm_hip_feed_finish", "nlzm_hip_feed_end",
     "nlzm_hip_block_placement", "nlzm_hip_get_counter",
     "nlzm_hip_decompress_dev", "nlzm_hip_decompress", "nlzm_hip_decompress_blocks_dev", "nlzm_hip_decompress_blocks", "nlzm_hip_verify_dev", "nlzm_hip_verify",
@@ -113,6 +113,9 @@ def load_library() -> C.CDLL:
     lib.nlzm_hip_blocks_step.argtypes = [C.c_uint32, u64p, C.POINTER(C.c_int), C.POINTER(C.c_double)]
     lib.nlzm_hip_blocks_finish.argtypes = [C.c_void_p, C.c_uint64, u64p, u64p]
     lib.nlzm_hip_blocks_abandon.restype = None
+    if hasattr(lib, "nlzm_hip_compress_blocks_bound"):     # (absent from older diagnostic builds loaded through NLZM_LIB)
+        lib.nlzm_hip_compress_blocks_bound.argtypes = [C.c_uint64, C.c_uint32]
+        lib.nlzm_hip_compress_blocks_bound.restype = C.c_uint64
     lib.nlzm_hip_compress_blocks.argtypes = [C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint64, u64p, u64p]
     lib.nlzm_hip_feed_begin.argtypes = [C.c_uint64, C.c_uint32]
     lib.nlzm_hip_feed.argtypes = [C.c_void_p, C.c_uint64]
@@ -187,12 +190,15 @@ def compress(data, hist_bits: int = 22) -> bytes:
 
 
 def compress_blocks(data, nblocks: int, hist_bits: int = 22) -> list[bytes]:
-    """k independent streams, all in flight on the one GPU (shard.block_range gives the byte ranges); the reference
+    """k independent streams (shard.block_range gives the byte ranges), 1 to 65536: in flight on the one GPU all at once while a launch holds
+    them (64 on an MI355X), more of them in sets one after another (option "container_set_blocks"; counter "container_sets"); the reference
     equivalent is encode_file (NLZM.cpp:1711) run on each range."""
     lib = load_library()
     src = np.ascontiguousarray(np.frombuffer(data, dtype=np.uint8) if not isinstance(data, np.ndarray) else data)
     n = int(src.size)
-    cap = int(lib.nlzm_hip_compress_bound(n)) + nblocks * (16 + 131072)
+    if not 1 <= nblocks <= 65536:
+        raise ValueError("nblocks: 1 to 65536")
+    cap = int(lib.nlzm_hip_compress_blocks_bound(n, nblocks))       # (a guaranteed bound; the pages the streams do not reach are never touched)
     dst = np.empty(cap, dtype=np.uint8)
     lens = (C.c_uint64 * nblocks)()
     out_len = C.c_uint64(0)

@@ -25,6 +25,7 @@
 #include "../../include/nlzm_hip.h"
 #include "nlzm_host_decode.h"
 #include "nlzm_read_plan.h"
+#include "nlzm_container_plan.h"       // (kMaxBlocks)
 
 namespace {
 
@@ -276,7 +277,7 @@ int main(int argc, char **argv)
             printf("Window bits: %d\n", hist_bits);
         } else if (!strncmp(arg, "blocks:", 7)) {
             const int v = atoi(arg + 7);
-            nblocks = (uint32_t)(v < 1 ? 1 : (v > 64 ? 64 : v));
+            nblocks = (uint32_t)(v < 1 ? 1 : (v > (int)nlzm::container::kMaxBlocks ? (int)nlzm::container::kMaxBlocks : v));
             printf("Blocks: %d\n", nblocks);
         } else if (!strncmp(arg, "gpus:", 5)) {
             const int v = atoi(arg + 5);
@@ -316,6 +317,7 @@ int main(int argc, char **argv)
         }
     }
     const int cmd = argc >= 2 ? (argv[1][0] | 0x20) : 0;
+    if (ngpus && nblocks > 64) { nblocks = 64; printf("Blocks: %d (on each GPU: a launch holds no more)\n", nblocks); }
     if (steps_k && !(on_gpu && ((argc == 4 && cmd == 'd') || (argc == 3 && cmd == 't')))) { printf("Error: -steps:K is for d -gpu and t -gpu\n"); return -1; }
     if (argc == 4 && cmd == 'c') {
         if (FILE *probe = fopen(argv[3], "rb")) { printf("Error: %s already exists\n", argv[3]); fclose(probe); return -1; }
@@ -398,7 +400,10 @@ int main(int argc, char **argv)
             nlzm_hip_shutdown();
             return 0;
         }
-        std::vector<uint8_t> out(nlzm_hip_compress_bound(in.size()) + (size_t)nstreams * (16 + 131072));
+        // room for the streams (a guaranteed bound: 9.7 GB at 65,536 blocks).  Not a vector: nothing is filled, and the pages behind the streams' end are never touched
+        const size_t out_room = ngpus ? (size_t)nlzm_hip_compress_bound(in.size()) + (size_t)nstreams * (16 + 131072) : (size_t)nlzm_hip_compress_blocks_bound(in.size(), nblocks);
+        struct Room { uint8_t *p; size_t n; uint8_t *data() const { return p; } size_t size() const { return n; } ~Room() { free(p); } } out{ (uint8_t *)malloc(out_room ? out_room : 1), out_room };
+        if (!out.data()) { printf("Error: no memory for %zu bytes of output\n", out_room); fclose(fout); remove(argv[3]); return -1; }
         std::vector<uint64_t> blen(nstreams);
         std::vector<int> devs;
         for (uint32_t d = 0; d < ngpus; d++) devs.push_back((int)d);
@@ -726,8 +731,9 @@ int main(int argc, char **argv)
                "\t-range:off:len [-range:...] x [input] [output] - (this build) write those byte ranges of what a block container holds; needs [input].idx\n"
                "Flags:\n"
                "\t-window:bits = Maximum window size in bits, default 22 (4 MB), min 15, max 28 (32 KB to 256 MB)\n"
-               "\t-blocks:k = (this build) compress k independent blocks at once; d/t read the streams back to back\n"
-               "\t-gpus:g = (this build) the blocks on GPUs 0..g-1 of this node, -blocks:k of them on each\n"
+               "\t-blocks:k = (this build) compress k independent blocks, 1 to 65536: as many at once as a launch holds (64), more of them\n"
+               "\t            in sets one after another; d/t read the streams back to back\n"
+               "\t-gpus:g = (this build) the blocks on GPUs 0..g-1 of this node, -blocks:k of them on each (64 at most)\n"
                "\t-verify = (this build) c decodes what it wrote on the GPU, one workgroup per stream, compares it with the input\n"
                "\t          and removes the output if they differ\n"
                "\t-gpu = (this build) d / t decode on the GPU, all blocks of a container at once (without it they run on the host); h hashes there\n"

@@ -28,8 +28,14 @@
 
 #include "xw.h"
 
+// The role can be built twice into one library: NLZM_DEC_NS names the namespace this inclusion's copy lives in, NLZM_DEC_RING its ring
+// (nlzm_decode_small.hip: nlzm::dec_small at 16 KiB beside nlzm::dec at 64 KiB).  StreamArgs and StreamResult are the same bytes in every copy.
+#ifndef NLZM_DEC_NS
+#define NLZM_DEC_NS dec
+#endif
+
 namespace nlzm {
-namespace dec {
+namespace NLZM_DEC_NS {
 
 #ifndef NLZM_DEC_RING
 #define NLZM_DEC_RING 65536
@@ -96,6 +102,7 @@ struct StreamResult {
     unsigned long long cycles, window_cycles, copy_cycles;         // wave cycles: in all, waiting for input windows, copying and flushing
     uint32_t why;                                   // written by the stepping form only: kWhy* of a pause, kWhyNone otherwise
 };
+static_assert(sizeof(StreamArgs) == 72 && sizeof(StreamResult) == 104, "one layout for every copy of the role: the host fills and reads them as nlzm::dec's");
 
 // c += d for a counter: kept in VGPRs (every lane the same value) -- the role's wave-uniform state fills the scalar registers as it is
 XW_FN void vadd(unsigned long long &c, unsigned long long d)
@@ -563,5 +570,5 @@ XW_FN void split_walk(const uint8_t *__restrict__ src, unsigned long long len, u
     }
 }
 
-}  // namespace dec
+}  // namespace NLZM_DEC_NS
 }  // namespace nlzm

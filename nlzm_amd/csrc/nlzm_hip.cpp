@@ -109,6 +109,8 @@ struct Options {
     int64_t test_fail_stream = 0;           // an error at once -- the fault path of a round that is queued behind a failing one
     int64_t block_ext_blocks = -1;          // test only ("block_ext_blocks"): extension blocks of a block-set stream's pair-list arena per launch (default: positions / 64 + 1024)
     int64_t report = 0;                     // 1: the stages' cycle accounting of every finished stream on stderr (nlzm_hip_set_option "stage_report")
+    int64_t container_set_blocks = 32;      // blocks per set of a container of more blocks than one launch holds ("container_set_blocks"; nlzm_container_plan.h)
+    int64_t decode_ring = 0;                // the one-shot decoder's LDS ring ("decode_ring"): 0 by the number of streams, 65536 / 16384 the big / the small kernel
 };
 
 // What the open stream runs with: resolved by stream_begin from the options as they were then, the stream's geometry and its place (by itself,
@@ -268,6 +270,7 @@ struct DevState {
     int64_t blocks_wb = 0;
     uint64_t blocks_per = 0;                        // bytes per block when the caller fixes the partition (0: ceil(n / nblocks))
     uint64_t redo_streams = 0;                      // streams of the last block set that were made again as single streams (their pair-list arena had run out)
+    uint64_t container_sets = 0;                    // block sets the last nlzm_hip_compress_blocks* call ran one after another (1: the blocks fitted one launch)
     // the rounds of the block set (blocks_step_impl): two are open at a time, and one may stay queued when a step returns
     struct Rounds {
         bool have = false;                          // round `q` is queued (pre-passes and launch) and not collected yet
@@ -291,6 +294,16 @@ DevState g_dev0;
 thread_local DevState *t_dev = nullptr;
 inline DevState &cur() { return t_dev ? *t_dev : g_dev0; }
 char *thread_err() { return t_dev ? t_dev->err : nullptr; }
+
+// Streams one persistent launch of this device holds, as nlzm_hip_blocks_begin fits them: three stage CUs (and the helper parsers' where
+// "block_parser_helper" is on) and one worker CU a stream, 64 at most -- 64 on an MI355X.  0 without a device.
+uint32_t blocks_capacity(const DevState &D)
+{
+    if (!D.ctx.inited) return 0;
+    const int64_t roles_live = (int64_t)pipeline2_role_blocks() - (D.opt.block_helper ? 0 : (int64_t)v2::kHelpers);
+    const int64_t cap = D.ctx.cu_count / (roles_live + 1);
+    return (uint32_t)(cap < 0 ? 0 : cap > 64 ? 64 : cap);
+}
 
 void free_stream_buffers(Ctx &C)
 {
@@ -783,6 +796,7 @@ int stream_finish(Ctx &C, uint64_t *dst_len, bool report)
 // ---- what the read side's entry points (nlzm_hip_decode.cpp, nlzm_hip_crc.cpp, nlzm_hip_range.cpp) use of this file's state: the error
 // text, the library's stream; what this file uses of theirs is declared in the same header ----
 #include "nlzm_host_util.h"
+#include "nlzm_container_plan.h"
 namespace nlzm {
 int host_error(int code, const char *text) { return set_err(code, "%s", text); }
 int host_stream(hipStream_t *st)
@@ -791,6 +805,11 @@ int host_stream(hipStream_t *st)
     if (!C.inited) return set_err(NLZM_HIP_E_NODEVICE, "nlzm_hip_init() has not succeeded (no device: there is no CPU fallback)");
     *st = C.st;
     return 0;
+}
+void host_decode_setup(int64_t *ring_option, int *cu_count)
+{
+    const DevState &D = cur();
+    *ring_option = D.opt.decode_ring; *cu_count = D.ctx.cu_count;
 }
 }  // namespace nlzm
 
@@ -960,6 +979,7 @@ int nlzm_hip_get_counter(const char *key, uint64_t *value)
     if (compress_counter(key, C.prof_last, C.wc_last, C.stats.positions, value)) return 0;
     if (!strcmp(key, "block_pool_bytes")) { *value = D.blocks_pool_size; return 0; }
     if (!strcmp(key, "block_redo_streams")) { *value = D.redo_streams; return 0; }
+    if (!strcmp(key, "container_sets")) { *value = D.container_sets; return 0; }
     if (!strcmp(key, "gpu_max_hw_queues_effective")) { *value = (uint64_t)g_hwq_effective; return 0; }
     return set_err(NLZM_HIP_E_ARG, "unknown counter %s", key);
 }
@@ -985,6 +1005,7 @@ void nlzm_hip_block_placement(uint32_t nstreams, uint32_t blocks_per_stream, uin
 enum OptKind { kOptRange,       // lo <= value <= hi
                kOptLanes,       // ... and a multiple of 64
                kOptFlag,        // stored as value != 0
+               kOptRing,        // 0, or one of the rings the one-shot decoder is built with
                kOptAny };       // stored as it is
 static const struct { const char *key; int64_t Options::*member; OptKind kind; int64_t lo, hi; } kOptions[] = {
     { "worker_blocks", &Options::worker_blocks, kOptRange, 1, 255 },
@@ -1005,6 +1026,8 @@ static const struct { const char *key; int64_t Options::*member; OptKind kind; i
     { "keep_block_pool", &Options::keep_pool, kOptFlag, 0, 0 },
     { "block_batch_chunks", &Options::block_batch, kOptRange, 1, 4096 },
     { "batch_chunks", &Options::batch, kOptRange, 1, 4096 },
+    { "container_set_blocks", &Options::container_set_blocks, kOptRange, 1, 64 },      // (... and the device's capacity, once it is known)
+    { "decode_ring", &Options::decode_ring, kOptRing, 0, 0 },
 };
 
 int nlzm_hip_set_option(const char *key, int64_t value)
@@ -1019,6 +1042,9 @@ int nlzm_hip_set_option(const char *key, int64_t value)
         if (strcmp(key, o.key)) continue;
         const bool ranged = o.kind == kOptRange || o.kind == kOptLanes;
         if (ranged && (value < o.lo || value > o.hi || (o.kind == kOptLanes && value % 64))) return set_err(NLZM_HIP_E_ARG, "%s out of range", key);
+        if (o.kind == kOptRing && value != 0 && value != 65536 && value != 16384) return set_err(NLZM_HIP_E_ARG, "%s: 0 (automatic), 65536 or 16384", key);
+        if (o.member == &Options::container_set_blocks && D.ctx.inited && value > (int64_t)blocks_capacity(D))
+            return set_err(NLZM_HIP_E_ARG, "%s out of range (this device holds %u streams at once)", key, blocks_capacity(D));
         D.opt.*o.member = o.kind == kOptFlag ? (int64_t)(value != 0) : value;
         if (o.member == &Options::keep_pool && !value && D.jobs.empty()) blocks_close(D, true);    // (the allocation a closed set left behind goes at once)
         return 0;
@@ -1522,8 +1548,21 @@ int nlzm_hip_blocks_finish(void *d_dst, uint64_t dst_cap, uint64_t *block_len, u
 
 void nlzm_hip_blocks_abandon(void) { blocks_close(cur()); }
 
-int nlzm_hip_compress_blocks_dev(const void *d_src, uint64_t n, uint32_t nblocks, uint32_t hist_bits_req, void *d_dst,
-                                 uint64_t dst_cap, uint64_t *block_len, uint64_t *dst_len)
+// Room that the streams of nblocks blocks of n bytes can take at most.  Up to 64 blocks (one set wherever a device holds them) the margin per
+// stream the entry points have always asked for; above that the sum of the blocks' own bounds, which is what a container compressed in sets is
+// guaranteed to fit (every set is bounded by its blocks' bounds).  No device needed.  0: nblocks out of range, or a sum beyond 64 bits.
+uint64_t nlzm_hip_compress_blocks_bound(uint64_t n, uint32_t nblocks)
+{
+    if (!nblocks || nblocks > container::kMaxBlocks) return 0;
+    if (nblocks <= 64) return nlzm_hip_compress_bound(n) + (uint64_t)nblocks * (16 + 131072);
+    container::Plan P;
+    if (container::make_plan(P, n, nblocks, 1, 1, nlzm_hip_compress_bound, ErrText{ nullptr, 0 })) return 0;
+    return P.out_bound;
+}
+
+// one block set from begin to finish: what the one-shot form has always been (the set's partition is the caller's, or D.blocks_per's)
+static int compress_block_set(const void *d_src, uint64_t n, uint32_t nblocks, uint32_t hist_bits_req, void *d_dst,
+                              uint64_t dst_cap, uint64_t *block_len, uint64_t *dst_len)
 {
     const auto t0 = std::chrono::steady_clock::now();
     int rc = nlzm_hip_blocks_begin(d_src, n, nblocks, hist_bits_req);
@@ -1542,6 +1581,59 @@ int nlzm_hip_compress_blocks_dev(const void *d_src, uint64_t n, uint32_t nblocks
     return rc;
 }
 
+// The sets of a container (nlzm_container_plan.h), one after another through compress_block_set with the partition fixed: set s compresses the
+// bytes of its blocks and writes their streams straight behind those of the set before it.  The block set's one allocation stays for the next
+// set ("keep_block_pool").  A set that fails has closed itself: the call ends with its error and nothing open.
+static int compress_container(DevState &D, const container::Plan &P, const void *d_src, uint32_t hist_bits_req, void *d_dst, uint64_t dst_cap,
+                              uint64_t *block_len, uint64_t *dst_len)
+{
+    static_assert(sizeof(nlzm_hip_stats) % sizeof(uint64_t) == 0 && alignof(nlzm_hip_stats) == alignof(uint64_t), "nlzm_hip_stats is uint64_t counters and nothing else: they are added up as an array");
+    nlzm_hip_stats total{};
+    uint64_t pos = 0, redo = 0;
+    // the sets share the one allocation whatever "keep_block_pool" says (46 GB freed and taken again 32 times otherwise): with the option off it
+    // goes when the call ends, as it does after any set then, and "block_pool_bytes" reads 0
+    const int64_t keep_pool = D.opt.keep_pool;
+    D.opt.keep_pool = 1;
+    struct Restore { DevState &D; int64_t keep; ~Restore() { D.opt.keep_pool = keep; if (!keep && D.jobs.empty()) blocks_close(D, true); } } restore{ D, keep_pool };
+    for (const container::Set &S : P.sets) {
+        uint64_t len = 0;
+        D.blocks_per = P.per;                       // (read and cleared by nlzm_hip_blocks_begin; a set wholly behind the input's end: empty streams)
+        const int rc = compress_block_set((const uint8_t *)d_src + S.off, S.len, S.count, hist_bits_req, (uint8_t *)d_dst + pos, dst_cap - pos,
+                                          block_len ? block_len + S.first : nullptr, &len);
+        D.blocks_per = 0;
+        if (rc) return rc;
+        pos += len;
+        redo += D.redo_streams;
+        D.container_sets++;
+        uint64_t *to = (uint64_t *)&total; const uint64_t *from = (const uint64_t *)&D.ctx.stats;   // counters of the whole container
+        for (size_t k = 0; k < sizeof(total) / 8; k++) to[k] += from[k];
+    }
+    D.ctx.stats = total;
+    D.redo_streams = redo;
+    *dst_len = pos;
+    return 0;
+}
+
+int nlzm_hip_compress_blocks_dev(const void *d_src, uint64_t n, uint32_t nblocks, uint32_t hist_bits_req, void *d_dst,
+                                 uint64_t dst_cap, uint64_t *block_len, uint64_t *dst_len)
+{
+    DevState &D = cur();
+    const uint32_t cap = blocks_capacity(D);
+    D.container_sets = 0;
+    // one set: no device yet (the set's own error), a partition the caller has fixed (a multi-device call: its limit per device stays), or blocks that fit one launch
+    if (!cap || D.blocks_per || nblocks <= cap) {
+        const int rc = compress_block_set(d_src, n, nblocks, hist_bits_req, d_dst, dst_cap, block_len, dst_len);
+        if (!rc) D.container_sets = 1;
+        return rc;
+    }
+    if (!d_dst || !dst_len) return set_err(NLZM_HIP_E_ARG, "null argument");
+    container::Plan P;
+    char text[256] = "";
+    const uint32_t set_blocks = (uint32_t)(D.opt.container_set_blocks < (int64_t)cap ? D.opt.container_set_blocks : (int64_t)cap);
+    if (const int rc = container::make_plan(P, n, nblocks, set_blocks, cap, nlzm_hip_compress_bound, ErrText{ text, sizeof text })) return set_err(rc, "%s", text);
+    return compress_container(D, P, d_src, hist_bits_req, d_dst, dst_cap, block_len, dst_len);
+}
+
 int nlzm_hip_compress_blocks(const uint8_t *src, uint64_t n, uint32_t nblocks, uint32_t hist_bits_req, uint8_t *dst,
                              uint64_t dst_cap, uint64_t *block_len, uint64_t *dst_len)
 {
@@ -1549,8 +1641,9 @@ int nlzm_hip_compress_blocks(const uint8_t *src, uint64_t n, uint32_t nblocks, u
     Ctx &C = D.ctx;
     if (!C.inited) return set_err(NLZM_HIP_E_NODEVICE, "nlzm_hip_init() has not succeeded");
     if ((!src && n) || !dst || !dst_len || !nblocks) return set_err(NLZM_HIP_E_ARG, "null argument");
+    if (nblocks > container::kMaxBlocks) return set_err(NLZM_HIP_E_ARG, "nblocks out of range (1 .. %u)", container::kMaxBlocks);
     uint8_t *d_in = nullptr, *d_out = nullptr;
-    const uint64_t bound = nlzm_hip_compress_bound(n) + (uint64_t)nblocks * (16 + 131072);
+    const uint64_t bound = nlzm_hip_compress_blocks_bound(n, nblocks);
     HIPCHK(hipMalloc(&d_in, n + 512));
     if (hipMalloc(&d_out, bound) != hipSuccess) { (void)hipFree(d_in); return set_err(NLZM_HIP_E_NOMEM, "output buffer"); }
     if (hipMemset(d_in + n, 0, 512) != hipSuccess || (n && hipMemcpy(d_in, src, n, hipMemcpyHostToDevice) != hipSuccess)) {

@@ -20,6 +20,7 @@ struct Last {
     double ms = 0;                                  // device time of all passes of the last call
     unsigned long long steps = 0;                   // launches of the open (or last) decode set
     double step_ms = 0;                             // device time of its last step
+    unsigned long long ring = 0;                    // LDS ring of the kernel the last decode launch ran
 };
 PerDevice<Last> g_last;
 
@@ -50,10 +51,21 @@ dec::StreamArgs decode_stream_args(const uint8_t *d_stream, uint64_t len, uint8_
     return dec::StreamArgs{ d_stream, len, d_dst, cap, (60ull + len / 1000000ull) * 100000000ull };
 }
 
-// one timed launch of the streams in `args`, by the one-shot kernel or by the stepping one; the call's device time and pass count go on
+// Which one-shot kernel a launch of k streams runs (option "decode_ring"): the 64 KiB ring fits a CU's LDS twice, so 2 x CUs streams are at work
+// at once and each wave has its SIMD to itself; with more streams than that the small ring's workgroups -- several to a SIMD, which hides the
+// lone wave's issue latency -- take over.  Up to 2 x CUs streams every launch is the kernel it has always been.
+static bool small_ring_for(size_t k)
+{
+    int64_t opt = 0; int cus = 0;
+    host_decode_setup(&opt, &cus);
+    return opt ? opt != (int64_t)dec::kRing : k > 2 * (size_t)cus;
+}
+
+// one timed launch of the streams in `args`, by a one-shot kernel or by the stepping one; the call's device time and pass count go on
 static int launch_streams(hipStream_t st, const std::vector<dec::StreamArgs> &args, std::vector<dec::StreamResult> &res, bool steps, float *ms)
 {
     const size_t k = args.size();
+    const bool small = !steps && small_ring_for(k);
     DevBuf da, dr;
     int rc = da.alloc(k * sizeof(dec::StreamArgs));
     if (!rc) rc = dr.alloc(k * sizeof(dec::StreamResult));
@@ -64,12 +76,13 @@ static int launch_streams(hipStream_t st, const std::vector<dec::StreamArgs> &ar
             const hipError_t e = hipMemcpyAsync(da.p, args.data(), k * sizeof(dec::StreamArgs), hipMemcpyHostToDevice, st);
             return e != hipSuccess ? e : hipMemsetAsync(dr.p, 0xFF, k * sizeof(dec::StreamResult), st);        // (a workgroup that never ran reports rc = -1)
         },
-        [&] { if (steps) launch_decode_steps(da.p, dr.p, (uint32_t)k, st); else launch_decode(da.p, dr.p, (uint32_t)k, st); },
+        [&] { if (steps) launch_decode_steps(da.p, dr.p, (uint32_t)k, st); else if (small) launch_decode_small(da.p, dr.p, (uint32_t)k, st); else launch_decode(da.p, dr.p, (uint32_t)k, st); },
         [&] { return hipMemcpyAsync(res.data(), dr.p, k * sizeof(dec::StreamResult), hipMemcpyDeviceToHost, st); });
     if (rc) return rc;
     Last &L = g_last.here();
     L.ms += *ms;
     L.passes++;
+    L.ring = small ? decode_small_ring() : dec::kRing;
     return 0;
 }
 
@@ -163,6 +176,7 @@ int decode_counter(const char *key, uint64_t *value)
     if (!strcmp(key, "decode_us")) { *value = (uint64_t)(L.ms * 1000.0 + 0.5); return 0; }
     if (!strcmp(key, "decode_steps")) { *value = L.steps; return 0; }
     if (!strcmp(key, "decode_step_us")) { *value = (uint64_t)(L.step_ms * 1000.0 + 0.5); return 0; }
+    if (!strcmp(key, "decode_ring_size")) { *value = L.ring; return 0; }
     if (!strcmp(key, "decode_state_bytes")) { *value = dec::kStateBytes; return 0; }      // (needs no device)
     return fail(NLZM_HIP_E_ARG, "unknown counter %s", key);
 }

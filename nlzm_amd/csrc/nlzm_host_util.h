@@ -23,8 +23,11 @@ namespace range { struct Args; }
 // nlzm_hip.cpp: the library's error text and its stream (an error if nlzm_hip_init has not succeeded)
 int host_error(int code, const char *text);
 int host_stream(hipStream_t *st);
-// nlzm_decode.hip, nlzm_crc.hip, nlzm_range.hip
+void host_decode_setup(int64_t *ring_option, int *cu_count);     // option "decode_ring" and the device's CUs (0 without a device)
+// nlzm_decode.hip, nlzm_decode_small.hip, nlzm_crc.hip, nlzm_range.hip
 void launch_decode(const void *d_args, void *d_res, uint32_t nstreams, hipStream_t st);
+void launch_decode_small(const void *d_args, void *d_res, uint32_t nstreams, hipStream_t st);      // the one-shot role with the small ring: the same args and results
+uint32_t decode_small_ring();                       // ... and the bytes of that ring
 void launch_decode_steps(const void *d_args, void *d_res, uint32_t nstreams, hipStream_t st);      // the stepping form: args carry state, max_frames, target
 void launch_split(const void *d_src, unsigned long long len, uint32_t nblocks, unsigned long long *d_block_len, uint32_t *d_bad, hipStream_t st);
 void launch_compare(const void *d_a, const void *d_b, unsigned long long n, unsigned long long *d_first, hipStream_t st);
