@@ -69,7 +69,7 @@ def build(force: bool = False) -> None:
     """Compile the gfx950 library and the CLI in-tree (hipcc cross-compiles without a GPU)."""
     if force:
         subprocess.run(["make", "-C", os.path.join(_HERE, "csrc"), "clean"], check=True, capture_output=True)
-    r = subprocess.run(["make", "-C", os.path.join(_HERE, "csrc"), "all"], capture_output=True, text=True)
+    r = subprocess.run(["make", "-C", os.path.join(_HERE, "csrc"), "-j8", "all"], capture_output=True, text=True)
     if r.returncode != 0:
         raise NlzmError("building libnlzm_hip.so failed:\n" + r.stdout + r.stderr)
 

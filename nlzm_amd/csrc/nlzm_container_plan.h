@@ -1,7 +1,7 @@
 // nlzm_container_plan.h -- what the HOST decides when a block container has more blocks than one persistent launch holds, with no device in
-// it: integers in, a table out.  nlzm_hip.cpp (nlzm_hip_compress_blocks_dev, nlzm_hip_compress_blocks) and the CPU harness
+// it: integers in, a table out.  nlzm_hip_blocks.cpp (nlzm_hip_blocks_begin, nlzm_hip_compress_blocks_dev), nlzm_hip_multi.cpp and the CPU harness
 // tests/host_sim/container_plan_sim.cpp include this one text, so that what the test proves is what the library runs:
-//   container::block_range   block i of the ceil(n / nblocks) partition (nlzm_amd/shard.py block_range, nlzm_hip_blocks_begin)
+//   container::block_range   block i of the ceil(n / nblocks) partition (nlzm_amd/shard.py block_range, nlzm_hip_blocks_begin; a device's part of a multi-GPU call)
 //   container::make_plan     the sets: which blocks in which set, each set's byte range, the bound of what the whole container may take
 // The sets run one after another, each through the block-set code with the partition fixed to `per` bytes a block; a set's streams go straight
 // behind those of the set before it.  Standard library only; compiles with plain g++ -std=c++17.
@@ -20,7 +20,7 @@ constexpr uint32_t kMaxBlocks = 65536;              // what every read-side entr
 constexpr uint32_t kDefaultSetBlocks = 32;          // option "container_set_blocks": an MI355X does best with 32 to 40 streams at once
 
 // block i of nblocks over n bytes, `per` = ceil(n / nblocks) bytes a block: [lo, lo + len), empty behind the input's end
-inline uint64_t per_block(uint64_t n, uint32_t nblocks) { return nblocks ? n / nblocks + (n % nblocks ? 1 : 0) : n; }   // (no n + nblocks - 1: it can wrap)
+inline uint64_t per_block(uint64_t n, uint64_t nblocks) { return nblocks ? n / nblocks + (n % nblocks ? 1 : 0) : n; }   // (no n + nblocks - 1: it can wrap)
 inline void block_range(uint64_t n, uint64_t per, uint32_t i, uint64_t &lo, uint64_t &len)
 {
     // (no i * per before it is known to fit: per > n / i says i * per > n, and the block starts at the input's end)

@@ -33,7 +33,7 @@ int crc_counter(const char *key, uint64_t *value)
 void crc_begin_call() { Last &L = g_last.here(); L.us = 0; L.bytes = 0; }
 
 // The CRC32 (from `seed`) of nranges ranges of the buffer at d_buf, on stream st; off / len / crc_out are host arrays.  Returns when the
-// CRCs are in crc_out.  Also what nlzm_hip_check* (nlzm_hip_decode.cpp) and nlzm_hip_feed_input_crc32 (nlzm_hip.cpp) call.
+// CRCs are in crc_out.  Also what nlzm_hip_check* (nlzm_hip_decode.cpp) and nlzm_hip_feed_input_crc32 (nlzm_hip_feed.cpp) call.
 int crc_ranges_on(hipStream_t st, const void *d_buf, uint64_t buf_len, uint32_t nranges, const uint64_t *off, const uint64_t *len, uint32_t seed,
                   uint32_t *crc_out)
 {

@@ -1,6 +1,6 @@
 // nlzm_hip_decode.cpp -- host side of the device decoder: the nlzm_hip_decompress* / nlzm_hip_verify_dev entry points of
 // include/nlzm_hip.h.  Kernels: nlzm_decode.hip; the role they run: nlzm_decode.h.  Uses the library's device, stream and error text
-// (nlzm_hip.cpp) and nothing else of the compress pipeline.
+// (nlzm_hip.cpp, through nlzm_host_util.h) and nothing else of the compress pipeline.
 #include <stdint.h>
 #include <string.h>
 

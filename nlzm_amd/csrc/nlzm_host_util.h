@@ -1,6 +1,7 @@
-// nlzm_host_util.h -- what the library's host files share (the -x hip ones: nlzm_hip.cpp, nlzm_hip_decode.cpp, nlzm_hip_crc.cpp,
-// nlzm_hip_range.cpp; nothing else includes this): the error and buffer scaffolding of the read side's entry points, the per-device
-// record of a call's counters, and THE prototypes of every function that crosses a file boundary -- a changed signature fails to compile.
+// nlzm_host_util.h -- what ALL the library's host files share (the -x hip ones: the compress side's through nlzm_host_state.h, and
+// nlzm_hip_decode.cpp, nlzm_hip_crc.cpp, nlzm_hip_range.cpp; nothing else includes this): the error and buffer scaffolding of the entry
+// points, the per-device record of a call's counters, and THE prototypes of every function that crosses the boundary between the compress
+// side and the read side -- a changed signature fails to compile.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -20,7 +21,7 @@ namespace dec { struct StreamArgs; struct StreamResult; }
 namespace crc { struct Args; }
 namespace range { struct Args; }
 
-// nlzm_hip.cpp: the library's error text and its stream (an error if nlzm_hip_init has not succeeded)
+// nlzm_hip.cpp: the library's error text (what fail and HIPCHK end in) and its stream (an error if nlzm_hip_init has not succeeded)
 int host_error(int code, const char *text);
 int host_stream(hipStream_t *st);
 void host_decode_setup(int64_t *ring_option, int *cu_count);     // option "decode_ring" and the device's CUs (0 without a device)
@@ -49,23 +50,22 @@ int decode_counter(const char *key, uint64_t *value);
 int crc_counter(const char *key, uint64_t *value);
 int range_counter(const char *key, uint64_t *value);
 
+constexpr size_t kErrText = 2048;                   // bytes of the library's error text, the terminator among them
 inline int fail(int code, const char *fmt, ...)
 {
-    char text[512];
+    char text[kErrText];
     va_list ap;
     va_start(ap, fmt);
     vsnprintf(text, sizeof text, fmt, ap);
     va_end(ap);
     return host_error(code, text);
 }
-#ifndef HIPCHK      // (nlzm_hip.cpp keeps its own, tied to its per-thread error text)
 #define HIPCHK(expr)                                                                                                        \
     do {                                                                                                                    \
         hipError_t e_ = (expr);                                                                                             \
         if (e_ != hipSuccess)                                                                                               \
             return fail(e_ == hipErrorOutOfMemory ? NLZM_HIP_E_NOMEM : NLZM_HIP_E_NODEVICE, "%s failed: %s", #expr, hipGetErrorString(e_)); \
     } while (0)
-#endif
 
 struct DevBuf {
     void *p = nullptr;

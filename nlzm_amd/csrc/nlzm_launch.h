@@ -1,4 +1,4 @@
-// nlzm_launch.h -- the launch wrappers of nlzm_kernels.hip, declared once: the host pipeline (nlzm_hip.cpp) calls them, and so does the
+// nlzm_launch.h -- the launch wrappers of nlzm_kernels.hip, declared once: the host pipeline (nlzm_hip.cpp, nlzm_hip_blocks.cpp, nlzm_hip_stage.cpp) calls them, and so does the
 // pre-pass probe (tests/prep_probe, test code), which is how the probe runs the kernels that ship and not copies of them.
 #pragma once
 #include <hip/hip_runtime.h>

@@ -1,6 +1,6 @@
 // nlzm_report.h -- what the compress pipeline says about itself, with no device in it: pure functions of the structs the device fills
 // (Persist::prof, WorkerCounters, v2::Hx; the slots' names are beside the structs, nlzm_core.h and nlzm_v2.h).  The library
-// (nlzm_hip.cpp) and a CPU harness (tests/host_sim/report_sim.cpp, held to tests/golden/report_*.txt) include this one text:
+// (nlzm_hip.cpp, nlzm_hip_blocks.cpp) and a CPU harness (tests/host_sim/report_sim.cpp, held to tests/golden/report_*.txt) include this one text:
 //   stage_report        the stages' accounting of a stream (option "stage_report")
 //   worker_report       ... and the worker lanes'
 //   kAcctRows, acct_figures   the eight cycles-per-position figures a block set's min / median / max table is made of, with their labels

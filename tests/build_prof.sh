@@ -5,7 +5,4 @@
 set -e
 cd "$(dirname "$0")/../nlzm_amd/csrc"
 d=$(mktemp -d); trap 'rm -rf "$d"' EXIT
-/opt/rocm/bin/hipcc -DNLZM_PROFILE $EXTRA -O3 -std=c++17 -fPIC --offload-arch=gfx950 -Wno-unused-function -Wno-unused-variable -c -o $d/k.o nlzm_kernels.hip &
-/opt/rocm/bin/hipcc -DNLZM_PROFILE $EXTRA -O3 -std=c++17 -fPIC --offload-arch=gfx950 -Wno-unused-function -Wno-unused-variable -Wno-undefined-inline -x hip -c -o $d/h.o nlzm_hip.cpp &
-wait
-/opt/rocm/bin/hipcc -shared -fPIC --offload-arch=gfx950 -o ../libnlzm_hip_prof.so $d/k.o $d/h.o
+make -j8 OBJDIR="$d" LIB=libnlzm_hip_prof.so EXTRA="-DNLZM_PROFILE $EXTRA" ../libnlzm_hip_prof.so

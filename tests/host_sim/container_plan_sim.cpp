@@ -96,6 +96,20 @@ int cmd_sweep()
             if (lo != want_lo || len != (n - want_lo < per ? n - want_lo : per) || len > n - lo) { printf("FAIL: block_range(n=%" PRIu64 ", nblocks=%u, i=%u)\n", n, nblocks, i); return 1; }
         }
     }
+    // The partition where the library once wrote it out by hand, lo = min(n, i * per) and hi = min(n, (i + 1) * per) in 64 bits (inputs below 2^32):
+    // nlzm_hip_blocks_begin with `per` fixed by the caller -- a set of a container or a device's share, so per is larger than ceil(n / nblocks),
+    // and a set lying wholly behind the input's end has n = 0 with per > 0: empty blocks at 0 -- and the multi-GPU call's part i of m blocks a
+    // device, [min(n, i * m * per), min(n, (i + 1) * m * per)), which is block i of m * per bytes a block.
+    for (uint64_t n : { (uint64_t)0, (uint64_t)1, (uint64_t)999, (uint64_t)1000, (uint64_t)1000001, (uint64_t)0xFFFEFFFFu }) for (uint32_t nblocks : { 1u, 2u, 7u, 32u, 64u }) {
+        const uint64_t ceil_per = container::per_block(n, nblocks);
+        for (uint64_t per : { ceil_per, ceil_per + 1, 2 * ceil_per + 3, n + 1, (uint64_t)0xFFFF0000u }) for (uint32_t m : { 1u, 3u, 64u }) for (uint32_t i = 0; i < nblocks; i++) {
+            const uint64_t step = per * m;          // (m = 1: a block of the set; m > 1: a device's part)
+            const uint64_t want_lo = (uint64_t)i * step < n ? (uint64_t)i * step : n, want_hi = (uint64_t)(i + 1) * step < n ? (uint64_t)(i + 1) * step : n;
+            uint64_t lo = 0, len = 0;
+            container::block_range(n, step, i, lo, len);
+            if (lo != want_lo || len != want_hi - want_lo) { printf("FAIL: block_range(n=%" PRIu64 ", per=%" PRIu64 ", i=%u) with the partition fixed\n", n, step, i); return 1; }
+        }
+    }
     if (container::make_plan(P0, ~0ull, 32, 32, 64, bound, ErrText{ nullptr, 0 }) != NLZM_HIP_E_ARG) { printf("FAIL: bounds that do not sum in 64 bits were summed\n"); return 1; }
     // what the plan refuses
     container::Plan P;

@@ -46,7 +46,7 @@ def test_sweep(sim):
 
 def test_library_and_harness_read_one_header():
     csrc = os.path.join(os.path.dirname(HERE), "nlzm_amd", "csrc")
-    assert '#include "nlzm_container_plan.h"' in open(os.path.join(csrc, "nlzm_hip.cpp")).read()
+    assert '#include "nlzm_container_plan.h"' in open(os.path.join(csrc, "nlzm_hip_blocks.cpp")).read()
     assert "nlzm_container_plan.h" in open(os.path.join(SIMDIR, "container_plan_sim.cpp")).read()
     text = open(os.path.join(csrc, "nlzm_container_plan.h")).read()
     assert "hip" not in text.lower().replace("nlzm_hip", "")          # no device in it
