@@ -328,6 +328,7 @@ __global__ __launch_bounds__(1024) void hot_select_kernel(const uint32_t *__rest
 // disjoint: slot (p & mask)*2 is written by p's own insertion and re-linked only by
 // later positions of the same head, NLZM.cpp:979-1021).
 // ---------------------------------------------------------------------------
+// isa-region: worker lanes
 struct LaneIO {
     static __device__ __forceinline__ void st_agent(uint32_t *p, uint32_t v)
     {
@@ -485,7 +486,52 @@ __device__ __forceinline__ void bt_descent(const BtView &B, uint32_t a, uint32_t
 //    store notes (slot, value it replaced) in the lane's list.  A decision as assumed releases what was held.  Otherwise the
 //    wave stops starting calls, lets the calls in flight finish, takes the stores of every call behind the position
 //    back, latest first, takes back or makes the position's own, and goes on behind it.
+//
 // ---------------------------------------------------------------------------
+// How a role of the persistent kernel gets at what the launch was given (struct Pipe2Args below: Geom, Globals, GlobalsV2 and the chunk range, as they
+// lie in the kernel's argument segment or in a block set's pack).  A role does not take them as values of the kernel: every role reads them, so the
+// compiler moved those loads in front of the branch that chooses the role -- some hundred scalar registers' worth, alive through every role whatever
+// it uses of them, parked in lanes of spare vector registers from where every use moved them back.  A role reads what IT uses
+// inside its branch, through a pointer the compiler cannot see through (role_args); and what only a rare branch of its loop uses, inside that branch,
+// through a pointer made opaque there again, so that it is not kept in a register across the loop.
+// ---------------------------------------------------------------------------
+#define NLZM_CONST_AS __attribute__((address_space(4)))
+#define NLZM_GLOBAL_AS __attribute__((address_space(1)))
+// (the role's number is part of the statement: identical ones in every branch would be merged in front of the branches again)
+template <uint32_t kRole, class P> __device__ __forceinline__ P role_args(P p)
+{
+    unsigned long long x = (unsigned long long)p;
+    asm volatile("; the arguments of role %1" : "+s"(x) : "n"(kRole));
+    return (P)x;
+}
+// pointers read from memory (a block set's pack): tell the compiler they are global ones (flat accesses would count on both wait counters)
+template <bool kFromMemory> __device__ __forceinline__ void global_pointers(Globals &G)
+{
+    if (!kFromMemory) return;
+#define NLZM_GLOBAL_PTR(p) p = (decltype(p))(NLZM_GLOBAL_AS std::remove_pointer_t<decltype(p)> *)(unsigned long long)(p)
+    NLZM_GLOBAL_PTR(G.in); NLZM_GLOBAL_PTR(G.rkhash); NLZM_GLOBAL_PTR(G.ht2); NLZM_GLOBAL_PTR(G.ht3); NLZM_GLOBAL_PTR(G.rk_table);
+    NLZM_GLOBAL_PTR(G.bt_heads); NLZM_GLOBAL_PTR(G.bt_tree); NLZM_GLOBAL_PTR(G.persist); NLZM_GLOBAL_PTR(G.syms); NLZM_GLOBAL_PTR(G.bits);
+    NLZM_GLOBAL_PTR(G.fmeta); NLZM_GLOBAL_PTR(G.cap_words); NLZM_GLOBAL_PTR(G.cap_used); NLZM_GLOBAL_PTR(G.bt_ready); NLZM_GLOBAL_PTR(G.bt_pairs); NLZM_GLOBAL_PTR(G.bt_ext); NLZM_GLOBAL_PTR(G.bt_ext_cur);
+    NLZM_GLOBAL_PTR(G.bt_flag); NLZM_GLOBAL_PTR(G.unc); NLZM_GLOBAL_PTR(G.bin_off); NLZM_GLOBAL_PTR(G.bin_pos); NLZM_GLOBAL_PTR(G.abort_word);
+    NLZM_GLOBAL_PTR(G.progress); NLZM_GLOBAL_PTR(G.wcnt); NLZM_GLOBAL_PTR(G.bt_undo); NLZM_GLOBAL_PTR(G.hot_of_bin); NLZM_GLOBAL_PTR(G.hot_list); NLZM_GLOBAL_PTR(G.hot_undo);
+}
+template <bool kFromMemory, class T> __device__ __forceinline__ T *global_pointer(T *p)
+{
+    return kFromMemory ? (T *)(NLZM_GLOBAL_AS T *)(unsigned long long)p : p;
+}
+template <bool kFromMemory> __device__ __forceinline__ void global_pointers(v2::GlobalsV2 &V)
+{
+    if (!kFromMemory) return;
+    NLZM_GLOBAL_PTR(V.ft); NLZM_GLOBAL_PTR(V.tp); NLZM_GLOBAL_PTR(V.tf); NLZM_GLOBAL_PTR(V.hx); NLZM_GLOBAL_PTR(V.state); NLZM_GLOBAL_PTR(V.hb);
+#undef NLZM_GLOBAL_PTR
+}
+// A wave-uniform value that only a rare branch reads again is kept in a vector register, where there is room, and not in one of the scalar
+// ones the steps of a loop are short of: parked() where it is made, unparked() where it is read.
+__device__ __forceinline__ uint32_t parked(uint32_t v) { asm volatile("" : "+v"(v)); return v; }
+__device__ __forceinline__ unsigned long long parked(unsigned long long v) { asm volatile("" : "+v"(v)); return v; }
+__device__ __forceinline__ uint32_t unparked(uint32_t v) { return (uint32_t)__builtin_amdgcn_readfirstlane((int)v); }
+__device__ __forceinline__ unsigned long long unparked(unsigned long long v) { return ((unsigned long long)unparked((uint32_t)(v >> 32)) << 32) | unparked((uint32_t)v); }
+// isa-region: hot-bin wave
 #ifndef NLZM_RISKY_AHEAD
 #define NLZM_RISKY_AHEAD 0
 #endif
@@ -503,29 +549,33 @@ constexpr uint32_t kPending = 0xFFFFFFFEu;      // (no position: stream_begin re
 // The window is loaded again behind its last entry once nothing undecided is parked in it; a wrong assumption loads it again where the bin
 // goes on.  Order: an entry's number in the chunk's list + 1 (`seq`), for calls and parked entries alike.
 __device__ __forceinline__ uint32_t wave_max_u32(uint32_t v) { return (uint32_t)__builtin_amdgcn_readlane((int)xw::scan_max(v), 63); }
-__device__ __forceinline__ void worker_role_hot(const Geom &g, const Globals &G, uint32_t c0, uint32_t c1, uint32_t bin, uint32_t hot_index)
+template <bool kFromMemory, class P>
+__device__ __forceinline__ void worker_role_hot(P args, const Geom &g, const Globals &G, uint32_t c0, uint32_t c1, uint32_t bin, uint32_t hot_index)
 {
     unsigned long long p0 = (unsigned long long)G.in, p1 = (unsigned long long)G.bt_heads, p2 = (unsigned long long)G.bt_tree,
                        p3 = (unsigned long long)G.bt_ready, p4 = (unsigned long long)G.bt_pairs, p5 = (unsigned long long)G.bt_flag,
                        p6 = (unsigned long long)G.hot_undo;
     uint32_t q0 = G.batch_a0, q2 = g.wmask, q3 = g.bt_tmask;
-    asm volatile("" : "+s"(p0), "+s"(p1), "+s"(p2), "+s"(p3), "+s"(p4), "+s"(p5), "+s"(p6));
+    asm volatile("" : "+s"(p0), "+s"(p1), "+s"(p2), "+s"(p5), "+s"(p6));
+    p3 = parked(p3); p4 = parked(p4);                               // (the records and the pair lists: touched once a call, parked between)
     asm volatile("" : "+s"(q0), "+s"(q2), "+s"(q3));
 #define NLZM_AS_GLOBAL(T, x) ((T *)(__attribute__((address_space(1))) T *)(x))
     const uint8_t *in = NLZM_AS_GLOBAL(const uint8_t, p0);
-    uint32_t *heads = NLZM_AS_GLOBAL(uint32_t, p1), *tree = NLZM_AS_GLOBAL(uint32_t, p2), *ready = NLZM_AS_GLOBAL(uint32_t, p3);
-    uint32_t *pairs = NLZM_AS_GLOBAL(uint32_t, p4);
+    uint32_t *heads = NLZM_AS_GLOBAL(uint32_t, p1), *tree = NLZM_AS_GLOBAL(uint32_t, p2);
+#define NLZM_HOT_READY NLZM_AS_GLOBAL(uint32_t, unparked(p3))
+#define NLZM_HOT_PAIRS NLZM_AS_GLOBAL(uint32_t, unparked(p4))
     const uint32_t *flags = NLZM_AS_GLOBAL(const uint32_t, p5);
     const uint32_t lane = threadIdx.x & 63u;
     unsigned long long *const undo = NLZM_AS_GLOBAL(unsigned long long, p6) + ((unsigned long long)hot_index * 64 + lane) * kUndoCap;
-#undef NLZM_AS_GLOBAL
     const uint32_t batch_a0 = q0, wmask = q2, tmask = q3;
-    BtView Bx{ in, heads, tree, ready, pairs, batch_a0, 0u, wmask, tmask };         // (for LaneSink::put: where a position's later pairs go)
-    Bx.pstride = G.bt_pstride; Bx.ext = G.bt_ext; Bx.ext_cur = G.bt_ext_cur; Bx.ext_cap = G.bt_ext_cap; Bx.fail_word = G.abort_word;
+    BtView Bx{ in, heads, tree, nullptr, nullptr, batch_a0, 0u, wmask, tmask };         // (for LaneSink::put: where a position's later pairs go)
+    Bx.pstride = G.bt_pstride;          // (where a position's fifth pair and later ones go: read where one turns up)
     enum : uint32_t { kIdle = 0, kStart = 1, kRun = 2, kHeld = 3 };
     enum : uint32_t { kwNone = 0, kwDone = 1, kwPark = 2, kwCall = 3 };             // a window entry: none / dropped or started / parked (undecided once passed) / a call to be started
     // the bin's entries of the chunk, in order (wave-uniform): the window starts at entry wb, entries below `cur` are passed
-    uint32_t c = c0, wb = 0, cur = 0, e0 = 0, la_end = 0;
+    // (which chunk the bin is in is looked at once a window at the most: parked)
+    uint32_t c = parked(c0), wb = 0, cur = 0, e0 = 0, la_end = 0;
+    const uint32_t c0p = parked(c0), c1p = parked(c1), binp = parked(bin);
     const uint32_t *pos = G.bin_pos;
     bool loaded = false, more = true, wvalid = false, rec = false;
     // the lane's window entry
@@ -548,14 +598,15 @@ __device__ __forceinline__ void worker_role_hot(const Geom &g, const Globals &G,
     // (counters of a launch: 32 bits each inside the loop -- a launch is a few hundred thousand steps -- but the two that add up whole calls)
     unsigned long long n_tests = 0, n_cmp = 0;
     uint32_t n_calls = 0, n_open = 0, n_back = 0, n_redo = 0;
-    uint32_t n_steps = 0, n_blk_risky = 0;
-    unsigned long long t_wait0 = 0;
-    uint32_t prog_seen = 0, steps = 0;
+    uint32_t n_steps = parked(0u), n_blk_risky = parked(0u);       // (the wave's, counted in a vector register)
+    unsigned long long t_wait0 = parked(0ull);                      // (the watchdog's: parked)
+    uint32_t prog_seen = parked(0u), steps = 0;
     // (accounting by the bin's size: WorkerCounters::hot_class)
     uint32_t k_work = 0, k_tests = 0, k_rep = 0, k_rec = 0, k_full = 0, k_blk = 0, k_noent = 0, k_skip = 0, k_und = 0;
-    const unsigned long long k_t0 = __builtin_readcyclecounter();
+    const unsigned long long k_t0 = parked((unsigned long long)__builtin_readcyclecounter());
     uint32_t k_total = 0;
     for (uint32_t cc = c0; cc < c1; cc++) { const uint32_t *off = G.bin_off + (unsigned long long)(cc - c0) * (G.nheads + 1); k_total += off[bin + 1] - off[bin]; }
+    k_total = parked(k_total);
 #ifdef NLZM_PROFILE
     unsigned long long t_sec[7] = {}, t_last = __builtin_readcyclecounter();
 #define NLZM_HOT_STAMP(k) do { const unsigned long long t_now = __builtin_readcyclecounter(); t_sec[k] += t_now - t_last; t_last = t_now; } while (0)
@@ -574,19 +625,22 @@ __device__ __forceinline__ void worker_role_hot(const Geom &g, const Globals &G,
         if (!wvalid && more && !rec) {
             for (;;) {
                 if (!loaded) {
-                    if (c >= c1) { more = false; break; }
-                    const uint32_t *off = G.bin_off + (unsigned long long)(c - c0) * (G.nheads + 1);
+                    const uint32_t cu = unparked(c), cfirst = unparked(c0p), bin_u = unparked(binp);
+                    if (cu >= unparked(c1p)) { more = false; break; }
+                    const P A = role_args<10>(args);                // (once a chunk: read here, not kept across the steps)
+                    const uint32_t *off = global_pointer<kFromMemory>(A->G.bin_off) + (unsigned long long)(cu - cfirst) * (A->G.nheads + 1);
                     // (every lane reads the same two words: said so, or the whole loop's control flow is compiled as if the lanes could part)
-                    cur = (uint32_t)__builtin_amdgcn_readfirstlane((int)off[bin]); e0 = (uint32_t)__builtin_amdgcn_readfirstlane((int)off[bin + 1]);
-                    const unsigned long long chunk_abs = (unsigned long long)c * g.chunk_size;
-                    const unsigned long long remain = g.n - chunk_abs;
-                    la_end = (uint32_t)(chunk_abs + (remain < g.feed ? remain : g.feed));
-                    pos = G.bin_pos + (unsigned long long)(c - c0) * g.chunk_size * 2;
+                    cur = (uint32_t)__builtin_amdgcn_readfirstlane((int)off[bin_u]); e0 = (uint32_t)__builtin_amdgcn_readfirstlane((int)off[bin_u + 1]);
+                    const uint32_t chunk_size = A->g.chunk_size, feed = A->g.feed;
+                    const unsigned long long chunk_abs = (unsigned long long)cu * chunk_size;
+                    const unsigned long long remain = A->g.n - chunk_abs;
+                    la_end = (uint32_t)(chunk_abs + (remain < feed ? remain : feed));
+                    pos = global_pointer<kFromMemory>(A->G.bin_pos) + (unsigned long long)(cu - cfirst) * chunk_size * 2;
                     loaded = true;
                 }
                 if (cur < e0) break;
                 if (__any(st != kIdle) || ovalid) break;            // (a wrong assumption would bring the bin back into this chunk)
-                c++; loaded = false;
+                c = parked(unparked(c) + 1); loaded = false;
             }
             if (more && loaded && cur < e0) {
                 wb = cur;
@@ -785,7 +839,7 @@ __device__ __forceinline__ void worker_role_hot(const Geom &g, const Globals &G,
                 started_now = true;
                 sp = v_word;                                        // :983
                 pend_l = (a & tmask) << 1; pend_r = pend_l + 1; len_l = 0; len_r = 0; tests = 0; cb = 0; cmp_off = 0;
-                sink.count = 0; sink.best = 1; sink.best_d = 0; sink.ext_idx = 0; sink.pairs = pairs + (unsigned long long)(a - batch_a0) * (2 * Bx.pstride);
+                sink.count = 0; sink.best = 1; sink.best_d = 0; sink.ext_idx = 0; sink.pairs = NLZM_HOT_PAIRS + (unsigned long long)(a - batch_a0) * (2 * Bx.pstride);
                 published = false;
                 undo[0] = (0x80000000u | hidx) | ((unsigned long long)sp << 32);
                 nu = 1;
@@ -816,7 +870,16 @@ __device__ __forceinline__ void worker_role_hot(const Geom &g, const Globals &G,
                 tests++;
                 cb += (l - init) + (full ? 0u : 1u);
                 const uint32_t d = a - sp;
-                if (l >= match_min(d) && l > sink.best) sink.put(Bx, d, l);  // :996-998
+                if (l >= match_min(d) && l > sink.best) {           // :996-998
+                    if (sink.count < 4) sink.put(Bx, d, l);
+                    else {
+                        const P A = role_args<13>(args);
+                        BtView Be = Bx;
+                        Be.ext = global_pointer<kFromMemory>(A->G.bt_ext); Be.ext_cur = global_pointer<kFromMemory>(A->G.bt_ext_cur); Be.ext_cap = A->G.bt_ext_cap;
+                        Be.fail_word = global_pointer<kFromMemory>(A->G.abort_word);
+                        sink.put(Be, d, l);
+                    }
+                }
                 if (full) { fin_now = true; fin_l = pl; fin_r = pr; }       // :1000-1004
                 else {
                     // :1006-1017.  The slot taken is marked before the store that makes its node reachable for later calls.
@@ -845,7 +908,7 @@ __device__ __forceinline__ void worker_role_hot(const Geom &g, const Globals &G,
         }
         // ---- a call that has ended: its result goes out when no undecided position stands before it
         if (st == kHeld && !wrong) {
-            if (!published && seq <= oseq) { sink.publish(ready + (unsigned long long)(a - batch_a0) * kBtRec, tests); published = true; }
+            if (!published && seq <= oseq) { sink.publish(NLZM_HOT_READY + (unsigned long long)(a - batch_a0) * kBtRec, tests); published = true; }
             if (published && !und && seq <= oseq) {
                 n_calls++; n_tests += tests; n_cmp += cb;
                 st = kIdle;
@@ -870,20 +933,24 @@ __device__ __forceinline__ void worker_role_hot(const Geom &g, const Globals &G,
 #endif
         // ---- watchdogs, every 4,096 steps (a launch that failed elsewhere; a position whose decision does not come while the finder stage stands)
         if ((++steps & 4095u) == 0) {
-            if (__any(LaneIO::ld_agent(G.abort_word) != 0)) break;
+            const P A = role_args<11>(args);
+            uint32_t *const abort_word = global_pointer<kFromMemory>(A->G.abort_word);
+            const uint32_t *const progress = global_pointer<kFromMemory>(A->G.progress);
+            if (__any(LaneIO::ld_agent(abort_word) != 0)) break;
             if (__any(und || w_und || o_und)) {
                 const unsigned long long now = wall_clock64();
-                const uint32_t prog = G.progress ? (uint32_t)__builtin_amdgcn_readfirstlane((int)LaneIO::ld_agent(G.progress)) : 0u;
-                if (!t_wait0 || prog != prog_seen) { t_wait0 = now; prog_seen = prog; }
-                else if (now - t_wait0 > 3000000000ull) { if (lane == 0) LaneIO::st_agent(G.abort_word, 2u); break; }
-            } else t_wait0 = 0;
+                const uint32_t prog = progress ? (uint32_t)__builtin_amdgcn_readfirstlane((int)LaneIO::ld_agent(progress)) : 0u;
+                if (!unparked(t_wait0) || prog != unparked(prog_seen)) { t_wait0 = parked(now); prog_seen = parked(prog); }
+                else if (now - unparked(t_wait0) > 3000000000ull) { if (lane == 0) LaneIO::st_agent(abort_word, 2u); break; }
+            } else t_wait0 = parked(0ull);
         }
         NLZM_HOT_STAMP(5);
         if (!more && !wvalid && !ovalid && !rec && !__any(st != kIdle)) break;
     }
+    WorkerCounters *const wcnt = global_pointer<kFromMemory>(role_args<12>(args)->G.wcnt);
     if (st != kIdle) {
-        atomicAdd(&G.wcnt->stuck_lanes, 1ull);
-        atomicMax(&G.wcnt->stuck_pos_inv, (unsigned long long)(uint32_t)~a);
+        atomicAdd(&wcnt->stuck_lanes, 1ull);
+        atomicMax(&wcnt->stuck_pos_inv, (unsigned long long)(uint32_t)~a);
     }
     unsigned long long t_calls = n_calls, t_open = n_open, t_back = n_back, t_redo = n_redo, t_skip = k_skip;
     for (int m = 32; m >= 1; m >>= 1) {
@@ -892,23 +959,28 @@ __device__ __forceinline__ void worker_role_hot(const Geom &g, const Globals &G,
         t_skip += __shfl_xor(t_skip, m, 64);
     }
     if (lane == 0) {
-        atomicAdd(&G.wcnt->bt_calls, t_calls); atomicAdd(&G.wcnt->bt_tests, n_tests); atomicAdd(&G.wcnt->cmp_bytes, n_cmp);
-        atomicAdd(&G.wcnt->dry_runs, t_open); atomicAdd(&G.wcnt->spec_calls, t_back); atomicAdd(&G.wcnt->spec_good, t_redo);
-        atomicAdd(&G.wcnt->hot_calls, t_calls);
-        atomicAdd(&G.wcnt->hot_steps, (unsigned long long)n_steps); atomicAdd(&G.wcnt->hot_blocked_risky, (unsigned long long)n_blk_risky);
+        atomicAdd(&wcnt->bt_calls, t_calls); atomicAdd(&wcnt->bt_tests, n_tests); atomicAdd(&wcnt->cmp_bytes, n_cmp);
+        atomicAdd(&wcnt->dry_runs, t_open); atomicAdd(&wcnt->spec_calls, t_back); atomicAdd(&wcnt->spec_good, t_redo);
+        atomicAdd(&wcnt->hot_calls, t_calls);
+        atomicAdd(&wcnt->hot_steps, (unsigned long long)unparked(n_steps)); atomicAdd(&wcnt->hot_blocked_risky, (unsigned long long)unparked(n_blk_risky));
         uint32_t kc = 0;
-        while (kc < 7 && (k_total >> (14 + kc))) kc++;
-        unsigned long long *hc = G.wcnt->hot_class[kc];
-        atomicAdd(&hc[kHcWaves], 1ull); atomicAdd(&hc[kHcCalls], t_calls); atomicAdd(&hc[kHcTests], n_tests); atomicAdd(&hc[kHcSteps], (unsigned long long)n_steps); atomicAdd(&hc[kHcTestSteps], (unsigned long long)k_work);
+        const uint32_t k_all = unparked(k_total);
+        while (kc < 7 && (k_all >> (14 + kc))) kc++;
+        unsigned long long *hc = wcnt->hot_class[kc];
+        atomicAdd(&hc[kHcWaves], 1ull); atomicAdd(&hc[kHcCalls], t_calls); atomicAdd(&hc[kHcTests], n_tests); atomicAdd(&hc[kHcSteps], (unsigned long long)unparked(n_steps)); atomicAdd(&hc[kHcTestSteps], (unsigned long long)k_work);
         atomicAdd(&hc[kHcLaneTests], (unsigned long long)k_tests); atomicAdd(&hc[kHcRepeats], (unsigned long long)k_rep); atomicAdd(&hc[kHcTakingBack], (unsigned long long)k_rec); atomicAdd(&hc[kHcAllHold], (unsigned long long)k_full); atomicAdd(&hc[kHcMayNotStart], (unsigned long long)k_blk);
-        atomicAdd(&hc[kHcNoEntry], (unsigned long long)k_noent); atomicAdd(&hc[kHcCycles], (unsigned long long)(__builtin_readcyclecounter() - k_t0)); atomicAdd(&hc[kHcSkipped], t_skip); atomicAdd(&hc[kHcIdleUndecided], (unsigned long long)k_und);
+        atomicAdd(&hc[kHcNoEntry], (unsigned long long)k_noent); atomicAdd(&hc[kHcCycles], (unsigned long long)(__builtin_readcyclecounter() - unparked(k_t0))); atomicAdd(&hc[kHcSkipped], t_skip); atomicAdd(&hc[kHcIdleUndecided], (unsigned long long)k_und);
 #ifdef NLZM_PROFILE
         for (uint32_t z = 0; z < kHcSecN; z++) atomicAdd(&hc[kHcSec + z], t_sec[z]);
 #endif
     }
 #undef NLZM_HOT_STAMP
+#undef NLZM_HOT_READY
+#undef NLZM_HOT_PAIRS
+#undef NLZM_AS_GLOBAL
 }
 
+// isa-region: worker lanes
 // A worker lane.  Bin b holds, in ascending order, the positions of every BT4 head h with h % bins == b; lane b walks it.
 //
 // Whether BT4 runs at a position the pre-filter marked is the finder stage's decision, and the lane is usually there first.
@@ -927,7 +999,8 @@ __device__ __forceinline__ void worker_role_hot(const Geom &g, const Globals &G,
 // of the calls behind the position are taken back, latest first, the position's own stores are taken back or made, and
 // the lane goes on from the position behind it.
 // Per call, in LDS (interleaved by thread): the first four record-setters and what the lane needs to publish or drop it.
-__device__ __forceinline__ void worker_role(const Geom &g, const Globals &G, uint32_t c0, uint32_t c1, uint32_t wblocks, uint32_t wblock)
+template <bool kFromMemory, class P>
+__device__ __forceinline__ void worker_role(P args, const Geom &g, const Globals &G, uint32_t c0, uint32_t c1, uint32_t wblocks, uint32_t wblock)
 {
     // The bin-taking lanes sit on the first NLZM_LPW lanes of the block's first waves: the lanes of a wave run their calls in lockstep, so a
     // lane that gets something to do waits for the longest call its wave is busy with -- the fewer lanes share a wave, the shorter.
@@ -938,7 +1011,7 @@ __device__ __forceinline__ void worker_role(const Geom &g, const Globals &G, uin
         if (!G.hot_list) return;
         const uint32_t k = ((threadIdx.x >> 6) - lane_waves) * wblocks + wblock;
         if (k >= G.hot_list[0]) return;
-        worker_role_hot(g, G, c0, c1, G.hot_list[1 + k], k);
+        worker_role_hot<kFromMemory>(args, g, G, c0, c1, G.hot_list[1 + k], k);
         return;
     }
     const uint32_t lane_in_block = (threadIdx.x >> 6) * kLpw + (threadIdx.x & 63u);
@@ -1119,6 +1192,7 @@ __device__ __forceinline__ void worker_role(const Geom &g, const Globals &G, uin
     }
 }
 
+// isa-region: kernel entry
 // ---------------------------------------------------------------------------
 // the persistent launch of the three-stage pipeline (nlzm_v2.h): blocks 0, 1, 2 of a stream are its finder, table and
 // parser stage (one wave each: the lanes are the positions of a block / the edges of two nodes), the others its BT4
@@ -1126,18 +1200,47 @@ __device__ __forceinline__ void worker_role(const Geom &g, const Globals &G, uin
 // block is resident at once (the stages wait on each other through progress words in HBM).
 // ---------------------------------------------------------------------------
 constexpr uint32_t kV2Roles = 3 + v2::kHelpers; // finder, table, parser, helper parsers (these leave at once where a stream has no HelpBox)
-__device__ __forceinline__ void pipeline2_roles(const Geom &g, const Globals &G, const v2::GlobalsV2 &V, uint32_t c0, uint32_t c1,
-                                                uint32_t local_block, uint32_t wblocks)
+// What a launch is given, as it lies in pipeline2_kernel's argument segment and at the head of a Stream2Args (read through role_args, above)
+struct Pipe2Args { Geom g; Globals G; v2::GlobalsV2 V; uint32_t c0, c1; };
+struct Stream2Args { Geom g; Globals G; v2::GlobalsV2 V; uint32_t c0, c1; v2::RoundSnap *snap; };
+static_assert(offsetof(Stream2Args, g) == offsetof(Pipe2Args, g) && offsetof(Stream2Args, G) == offsetof(Pipe2Args, G) && offsetof(Stream2Args, V) == offsetof(Pipe2Args, V) &&
+              offsetof(Stream2Args, c0) == offsetof(Pipe2Args, c0) && offsetof(Stream2Args, c1) == offsetof(Pipe2Args, c1), "a Stream2Args starts with a Pipe2Args");
+template <bool kFromMemory, class R, class P> __device__ __forceinline__ void stage_args(R &r, P a)
+{
+    __builtin_memcpy(&r.g, &a->g, sizeof(Geom)); __builtin_memcpy(&r.G, &a->G, sizeof(Globals)); __builtin_memcpy(&r.V, &a->V, sizeof(v2::GlobalsV2));
+    global_pointers<kFromMemory>(r.G); global_pointers<kFromMemory>(r.V);
+}
+// kFromMemory: `args` points into a block set's pack in device memory; otherwise into the kernel's argument segment
+template <bool kFromMemory, class P> __device__ __forceinline__ void pipeline2_roles(P args, uint32_t local_block, uint32_t wblocks)
 {
     if (local_block < kV2Roles) {
         // finder: one wave; table: kTW or kTWWide waves (the shape the launch before chose), a block each; parser: kPW waves on the same block
-        if (threadIdx.x >= (local_block >= 2 ? v2::kParserThreads : (local_block == 1 ? 64u * v2::table_waves(((const v2::StateV2 *)V.state)->tb_wide[G.launch_par & 1u]) : 64u))) return;
-        if (local_block == 0) { v2::Finder r; r.g = g; r.G = G; r.V = V; r.run(c0, c1); }
-        else if (local_block == 1) { v2::Table r; r.g = g; r.G = G; r.V = V; r.run(c0, c1); }
-        else if (local_block == 2) { v2::Parser r; r.g = g; r.G = G; r.V = V; r.run(c0, c1); }
-        else if (V.hb) { v2::Parser r; r.g = g; r.G = G; r.V = V; r.run_helper(c0, local_block - 3); }
+        if (local_block == 0) {
+            if (threadIdx.x >= 64u) return;
+            const P a = role_args<0>(args);
+            v2::Finder r; stage_args<kFromMemory>(r, a); r.run(a->c0, a->c1);
+        } else if (local_block == 1) {
+            const P a = role_args<1>(args);
+            v2::Table r; stage_args<kFromMemory>(r, a);
+            if (threadIdx.x >= 64u * v2::table_waves(((const v2::StateV2 *)r.V.state)->tb_wide[r.G.launch_par & 1u])) return;
+            r.run(a->c0, a->c1);
+        } else {
+            if (threadIdx.x >= v2::kParserThreads) return;
+            if (local_block == 2) {
+                const P a = role_args<2>(args);
+                v2::Parser r; stage_args<kFromMemory>(r, a); r.run(a->c0, a->c1);
+            } else {
+                const P a = role_args<3>(args);
+                v2::Parser r; stage_args<kFromMemory>(r, a);
+                if (r.V.hb) r.run_helper(a->c0, local_block - 3);
+            }
+        }
     } else {
-        worker_role(g, G, c0, c1, wblocks, local_block - kV2Roles);
+        const P a = role_args<4>(args);
+        Geom g; Globals G;
+        __builtin_memcpy(&g, &a->g, sizeof(Geom)); __builtin_memcpy(&G, &a->G, sizeof(Globals));
+        global_pointers<kFromMemory>(G);
+        worker_role<kFromMemory>(a, g, G, a->c0, a->c1, wblocks, local_block - kV2Roles);
     }
 }
 __global__ __launch_bounds__(512) void pipeline2_kernel(Geom g, Globals G, v2::GlobalsV2 V, uint32_t c0, uint32_t c1)
@@ -1147,25 +1250,17 @@ __global__ __launch_bounds__(512) void pipeline2_kernel(Geom g, Globals G, v2::G
     const bool spread = gridDim.x > 8 * (kV2Roles - 1);                                   // (a small grid: the first blocks are the stages)
     const uint32_t before = b ? (b + 7) / 8 < kV2Roles ? (b + 7) / 8 : kV2Roles : 0u;     // stage blocks below b
     const uint32_t local = (b % 8 == 0 && b / 8 < kV2Roles && spread) ? b / 8 : (spread ? kV2Roles + (b - before) : b);
-    pipeline2_roles(g, G, V, c0, c1, local, gridDim.x - kV2Roles);
+    // (the explicit arguments are the head of the argument segment, each at its own alignment: the layout of a Pipe2Args)
+    (void)g; (void)G; (void)V; (void)c0; (void)c1;
+    pipeline2_roles<false>((const NLZM_CONST_AS Pipe2Args *)__builtin_amdgcn_kernarg_segment_ptr(), local, gridDim.x - kV2Roles);
 }
-struct Stream2Args { Geom g; Globals G; v2::GlobalsV2 V; uint32_t c0, c1; v2::RoundSnap *snap; };
 constexpr uint32_t kMaxStreams2PerLaunch = 64;          // (the pack lives in device memory: the kernel-argument segment holds 4 KB)
 __global__ __launch_bounds__(512) void pipeline2_multi_kernel(const Stream2Args *__restrict__ pack, uint32_t bps)
 {
     uint32_t s, local;
     multi_block_of(gridDim.x, bps, blockIdx.x, s, local);       // (a stream's blocks on one XCD: nlzm_core.h)
-    Stream2Args a = pack[s];
-    // pointers read from memory: tell the compiler they are global ones (flat accesses would count on both wait counters)
-#define NLZM_GLOBAL_PTR(p) p = (decltype(p))(__attribute__((address_space(1))) std::remove_pointer_t<decltype(p)> *)(unsigned long long)(p)
-    NLZM_GLOBAL_PTR(a.G.in); NLZM_GLOBAL_PTR(a.G.rkhash); NLZM_GLOBAL_PTR(a.G.ht2); NLZM_GLOBAL_PTR(a.G.ht3); NLZM_GLOBAL_PTR(a.G.rk_table);
-    NLZM_GLOBAL_PTR(a.G.bt_heads); NLZM_GLOBAL_PTR(a.G.bt_tree); NLZM_GLOBAL_PTR(a.G.persist); NLZM_GLOBAL_PTR(a.G.syms); NLZM_GLOBAL_PTR(a.G.bits);
-    NLZM_GLOBAL_PTR(a.G.fmeta); NLZM_GLOBAL_PTR(a.G.cap_words); NLZM_GLOBAL_PTR(a.G.cap_used); NLZM_GLOBAL_PTR(a.G.bt_ready); NLZM_GLOBAL_PTR(a.G.bt_pairs); NLZM_GLOBAL_PTR(a.G.bt_ext); NLZM_GLOBAL_PTR(a.G.bt_ext_cur);
-    NLZM_GLOBAL_PTR(a.G.bt_flag); NLZM_GLOBAL_PTR(a.G.unc); NLZM_GLOBAL_PTR(a.G.bin_off); NLZM_GLOBAL_PTR(a.G.bin_pos); NLZM_GLOBAL_PTR(a.G.abort_word);
-    NLZM_GLOBAL_PTR(a.G.progress); NLZM_GLOBAL_PTR(a.G.wcnt); NLZM_GLOBAL_PTR(a.G.bt_undo); NLZM_GLOBAL_PTR(a.G.hot_of_bin); NLZM_GLOBAL_PTR(a.G.hot_list); NLZM_GLOBAL_PTR(a.G.hot_undo);
-    NLZM_GLOBAL_PTR(a.V.ft); NLZM_GLOBAL_PTR(a.V.tp); NLZM_GLOBAL_PTR(a.V.tf); NLZM_GLOBAL_PTR(a.V.hx); NLZM_GLOBAL_PTR(a.V.state); NLZM_GLOBAL_PTR(a.V.hb);
-#undef NLZM_GLOBAL_PTR
-    pipeline2_roles(a.g, a.G, a.V, a.c0, a.c1, local, bps - kV2Roles);
+    // (read as constant memory: the pack is written before the launch and by nothing in it, and these are scalar loads whatever stands in front of them)
+    pipeline2_roles<true>((const NLZM_CONST_AS Stream2Args *)(unsigned long long)(pack + s), local, bps - kV2Roles);
 }
 // Either side of a shared launch whose successor is queued before the host has looked at it (nlzm_hip.cpp, blocks_step_impl):
 // round_open sets every stream's progress words to the launch's first position (what step_pre's copy does for a launch of its own),

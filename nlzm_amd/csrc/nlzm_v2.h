@@ -89,8 +89,10 @@ struct RoundSnap { uint32_t error, next_chunk, aborted, pad; Hx hx; };
 #ifndef NLZM_HELPERS
 #define NLZM_HELPERS 2
 #endif
-constexpr uint32_t kHelpers = NLZM_HELPERS;     // (1, 2 or 3.  Three, measured in round 6: the parser stage's busy cycles 305 -> 266 per position, the headline 6.35 -> 6.40 MB/s -- the finder stage
-                                                //  bounds the stream there; not the default, one CU more for 0.7 %: DESIGN.md section 13)
+constexpr uint32_t kHelpers = NLZM_HELPERS;     // (1, 2 or 3.  Three, measured in round 6: the parser stage's busy cycles 305 -> 266 per position, the headline 6.35 -> 6.40 MB/s, 0.7 %, the
+                                                //  finder stage bounding the stream.  Measured again once the roles read their own arguments: 6.540 -> 6.823 MB/s,
+                                                //  4.3 % and 10.7 times the spread of the two-helper runs -- the finder is no longer what three helpers run into.  Still two here: one CU more
+                                                //  per stream is not measured on the block leg, the workloads and the suites yet, and the default changes with those, not before)
 static_assert(kHelpers >= 1 && kHelpers <= 3, "Hx::hw holds three helpers' words");
 // helper k's first node (a segment that is cut at 4,096: one helper -- the front 2,400 nodes stay with the parser stage, the helper has
 // 1,792 .. 4,096; two -- 1,900 / 1,280 .. 3,100 / 2,496 .. 4,096; the helpers further back wait for their records longer)
@@ -198,6 +200,7 @@ XW_FN bool wait_word_ge(const uint32_t *w, uint32_t v, Hx *hx, uint32_t code)
 // =================================================================================================
 // finder stage
 // =================================================================================================
+// isa-region: finder block
 struct FLds {
     uint32_t ht2[4096];                         // :1750
     uint32_t ht3[16384 + 8];                    // :1751 (bucket b uses rows b and b+1, :912: 2^14 + 1 rows are ever touched)
@@ -222,15 +225,28 @@ struct Finder {
     uint32_t rk_cut = 0;        // the carried RK256 match is shorter than the bytes agree: the uint16 length parameter ended its compare (:760, :1096)
     uint32_t prev_nice, seg_s;
     uint32_t gap_last = 0;      // the last position that no match found in front of it reaches beyond (where a segment ends unless a rep probe carried it further, :1598-1628), or the chunk's start
-    uint32_t n_seg_own = 0, n_seg_wait = 0;     // starts of nice regions whose segment this stage knew itself / had to wait for
     uint32_t t_pos_seen;
     uint32_t err;
     uint32_t dbg_a = 0;         // start of the block being evaluated (error dump)
-    unsigned long long n_pos, n_nice, n_unc, n_ht, n_rkp, n_rki, n_cmp, n_blocks, n_cut0, n_cut1, n_cut2, n_cut3, n_cut4, n_cut5;
-    unsigned long long n_cmp_lane = 0;          // bytes compared, per lane
+    // The launch's counters are kept PER LANE and summed over the wave when the launch ends: a lane counts its own positions with one vector add where
+    // the wave's count was a ballot, a population count and a 64-bit scalar add -- and two dozen wave-uniform counters alive across block() were two
+    // dozen pairs of scalar registers the block's own values were moved out of the way for.  32 bits: a lane's share of a launch.
+    uint32_t n_pos = 0, n_nice = 0, n_unc = 0, n_ht = 0, n_rkp = 0, n_rki = 0;
+    unsigned long long n_cmp_lane = 0;          // bytes compared
     unsigned long long t_wait, t_wait_bt = 0, t_total;
     uint32_t n_so_top = 0, n_so_tie = 0, n_so_won = 0;  // cut-short RK256 entries that became the growing top entry; that ended exactly where another entry ends; and won that
-    uint32_t n_late_unc = 0, n_late_other = 0, n_late_hot = 0, n_late_first = 0, n_late_blocks = 0;
+    uint32_t n_late_unc = 0, n_late_other = 0, n_late_hot = 0;
+    // ... and what the WAVE counts, in the lanes of one register: lane k holds counter k
+    enum : uint32_t { kWcCut0 = 0, kWcBlocks = 6, kWcLateFirst = 7, kWcLateBlocks = 8, kWcSegOwn = 9, kWcSegWait = 10 };   // (kWcCut0 + w: blocks cut for reason w, 0..5)
+    uint32_t n_wave = 0;
+    XW_FN void count(uint32_t k, uint32_t v = 1) { n_wave += xw::lane() == k ? v : 0u; }
+    XW_FN unsigned long long counted(uint32_t k) const { return xw::readlane(n_wave, k); }
+    XW_FN unsigned long long lane_sum(uint32_t v) const
+    {
+        unsigned long long t = v;
+        for (uint32_t d = 32; d; d >>= 1) t += xw::shfl64(t, xw::lane() ^ d);
+        return xw::readfirst64(t);
+    }
     unsigned long long t_f[kPfFinderSecN] = {}; // profile build: cycles per section of block()
 #ifdef NLZM_PROFILE
     XW_FN unsigned long long ptick() const { return xw::tick(); }
@@ -323,7 +339,7 @@ struct Finder {
                     if (covered || own) {
                         xw::after_poll();
                         seg_s = sa;
-                        n_seg_own += own; n_seg_wait += spins != 0;
+                        count(kWcSegOwn, own); count(kWcSegWait, spins != 0);
                         xw::trace(1, a0, seg_s, (uint32_t)ps);
                         break;
                     }
@@ -355,7 +371,7 @@ struct Finder {
                 for (uint32_t e = (rk_end | 255u) + 1; e < q0 + 256; e += 256) {
                     const uint32_t hh = xw::readfirst(G.rkhash[base + e - 256]);
                     if (i == 0) G.rk_table[hh >> g.rk_shift] = q0 | (hh << g.wbits);
-                    n_rki++;
+                    n_rki += i == 0;
                 }
                 xw::drain();
             }
@@ -633,13 +649,12 @@ struct Finder {
                 }
                 const unsigned long long missing = xw::ballot(!have);
                 if (waits && spins == 0) {       // (accounting: whose results are not there when the block asks first)
-                    n_late_unc += (uint32_t)__builtin_popcountll(missing & xw::ballot(unc));
-                    n_late_other += (uint32_t)__builtin_popcountll(missing & ~xw::ballot(unc));
+                    n_late_unc += !have && unc;
+                    n_late_other += !have && !unc;
                     if (missing) {      // ... of a hot bin's wave or of a lane; lane 0 of the block (the position a block was cut at) or a later one
                         const bool hot = G.hot_of_bin && !have && G.hot_of_bin[(hash4(v4) >> g.bt_shift) % G.nheads] != 0;
-                        n_late_hot += (uint32_t)__builtin_popcountll(xw::ballot(hot));
-                        n_late_first += (uint32_t)(missing & 1ull);
-                        n_late_blocks++;
+                        n_late_hot += hot;
+                        count(kWcLateFirst, (uint32_t)(missing & 1ull)); count(kWcLateBlocks);
                     }
                 }
                 const uint32_t F = missing ? (uint32_t)__builtin_ctzll(missing) : 64u;          // the first lane whose result is missing
@@ -714,11 +729,10 @@ struct Finder {
 
         const unsigned long long f6 = ptick();
         if (m == 0) { fail(kErrInternal, a0, 7); return 1; }
-        n_blocks++;
+        count(kWcBlocks);
         if (m < n) {        // (why the block was cut; diagnostics)
-            // (adds, not a chain of branches: the compiler turns the chain into ONE indexed access and the stage's state goes to scratch)
             const uint32_t w = m == cut_nice ? 0u : (m == jo + 1 ? 1u : (m == cut_ev ? 2u : (m == cut_rk ? 3u : (m == cut_bin ? 5u : 4u))));
-            n_cut0 += w == 0; n_cut1 += w == 1; n_cut2 += w == 2; n_cut3 += w == 3; n_cut4 += w == 4; n_cut5 += w == 5;
+            count(kWcCut0 + w);
         }
         const bool fin = i < m;
         {   // the last position that nothing found in front of it reaches beyond (the segment start of a later nice region, above)
@@ -726,8 +740,7 @@ struct Finder {
             if (gapm) gap_last = a0 + (63u - (uint32_t)__builtin_clzll(gapm));
         }
         if (stm || xw::any(so_tie)) {       // (accounting)
-            n_so_top += (uint32_t)__builtin_popcountll(xw::ballot(fin && so_top)); n_so_tie += (uint32_t)__builtin_popcountll(xw::ballot(fin && so_tie));
-            n_so_won += (uint32_t)__builtin_popcountll(xw::ballot(fin && so_win));
+            n_so_top += fin && so_top; n_so_tie += fin && so_tie; n_so_won += fin && so_win;
         }
 
         // a position that the pre-filter promised to be a BT4 position must not be nice
@@ -785,12 +798,12 @@ struct Finder {
             }
         }
         // counters
-        n_pos += m;
-        n_nice += (unsigned long long)__builtin_popcountll(xw::ballot(fin && nice_real));
-        n_unc += (unsigned long long)__builtin_popcountll(xw::ballot(fin && unc && avail >= 4));
-        n_ht += (unsigned long long)__builtin_popcountll(xw::ballot(fin && ht_call));
-        n_rkp += (unsigned long long)__builtin_popcountll(xw::ballot(fin && rk_probe));
-        n_rki += (unsigned long long)__builtin_popcountll(xw::ballot(fin && rk_call && (q & 255u) == 0));
+        n_pos += fin;
+        n_nice += fin && nice_real;
+        n_unc += fin && unc && avail >= 4;
+        n_ht += fin && ht_call;
+        n_rkp += fin && rk_probe;
+        n_rki += fin && rk_call && (q & 255u) == 0;
         n_cmp_lane += fin ? cmpb : 0u;                              // (summed over the lanes once, when the launch ends: six dependent shuffles per block otherwise)
         pend_fpos = a0 + m;                                         // (said by flush_fpos)
         // the next block's own loads (same chunk: same lookahead end)
@@ -811,6 +824,7 @@ struct Finder {
         return m;
     }
 
+    // isa-region: finder chunk loop
     XW_FN void run(uint32_t c0, uint32_t c1)
     {
         FLds *L = xw::lds<FLds>();
@@ -829,8 +843,6 @@ struct Finder {
         rk_cut = rk_len >> 31; rk_len &= 0x7FFFFFFFu;                       // (the length is at most 65,535)
         err = xw::readfirst(P->error);
         if (!err && G.test_fail) fail(kErrInternal + 50, (uint32_t)((unsigned long long)c0 * g.chunk_size), 9);      // (test of the fault path: option "test_fail_stream")
-        n_pos = n_nice = n_unc = n_ht = n_rkp = n_rki = n_cmp = n_blocks = 0;
-        n_cut0 = n_cut1 = n_cut2 = n_cut3 = n_cut4 = n_cut5 = 0;
         t_wait = 0;
         const unsigned long long t_start = xw::tick();
         t_pos_seen = (uint32_t)((unsigned long long)c0 * g.chunk_size);
@@ -867,8 +879,15 @@ struct Finder {
             }
         }
         flush_fpos();
+        // (the lanes' counters, summed: every lane is still here)
         for (uint32_t d = 32; d; d >>= 1) n_cmp_lane += xw::shfl64(n_cmp_lane, i ^ d);
-        n_cmp += xw::readfirst64(n_cmp_lane);
+        const unsigned long long s_cmp = xw::readfirst64(n_cmp_lane);
+        const unsigned long long s_pos = lane_sum(n_pos), s_nice = lane_sum(n_nice), s_unc = lane_sum(n_unc), s_ht = lane_sum(n_ht), s_rkp = lane_sum(n_rkp), s_rki = lane_sum(n_rki);
+        const unsigned long long s_so_top = lane_sum(n_so_top), s_so_tie = lane_sum(n_so_tie), s_so_won = lane_sum(n_so_won);
+        const unsigned long long s_late_unc = lane_sum(n_late_unc), s_late_other = lane_sum(n_late_other), s_late_hot = lane_sum(n_late_hot);
+        const unsigned long long s_blocks = counted(kWcBlocks), s_cut0 = counted(kWcCut0), s_cut1 = counted(kWcCut0 + 1), s_cut2 = counted(kWcCut0 + 2), s_cut3 = counted(kWcCut0 + 3),
+                                 s_cut4 = counted(kWcCut0 + 4), s_cut5 = counted(kWcCut0 + 5), s_late_first = counted(kWcLateFirst), s_late_blocks = counted(kWcLateBlocks),
+                                 s_seg_own = counted(kWcSegOwn), s_seg_wait = counted(kWcSegWait);
         xw::wave_sync();
         // (opaque: or the 64 store addresses are computed when the launch begins, kept through it, and one of them spilled)
         for (uint32_t k = xw::opaque(i); k < 4096; k += 64) G.ht2[k] = L->ht2[k];
@@ -881,19 +900,19 @@ struct Finder {
             // (every stage adds the counters it owns, with agent-scope atomics: the stages run on different CUs, in
             //  block mode on different XCDs, and finish within microseconds of each other)
             Counters &c = P->cnt;
-            xw::atomic_add64_agent(&c.positions, n_pos); xw::atomic_add64_agent(&c.nice_positions, n_nice);
-            xw::atomic_add64_agent(&c.uncertain_positions, n_unc); xw::atomic_add64_agent(&c.ht_rows, 3 * n_ht);
-            xw::atomic_add64_agent(&c.rk_probes, n_rkp); xw::atomic_add64_agent(&c.rk_inserts, n_rki);
-            xw::atomic_add64_agent(&c.cmp_bytes, n_cmp); xw::atomic_add64_agent(&c.shifts, shifts);
+            xw::atomic_add64_agent(&c.positions, s_pos); xw::atomic_add64_agent(&c.nice_positions, s_nice);
+            xw::atomic_add64_agent(&c.uncertain_positions, s_unc); xw::atomic_add64_agent(&c.ht_rows, 3 * s_ht);
+            xw::atomic_add64_agent(&c.rk_probes, s_rkp); xw::atomic_add64_agent(&c.rk_inserts, s_rki);
+            xw::atomic_add64_agent(&c.cmp_bytes, s_cmp); xw::atomic_add64_agent(&c.shifts, shifts);
             unsigned long long *pr = P->prof;
-            xw::atomic_add64_agent(&pr[kPfFinderBlocks], n_blocks); xw::atomic_add64_agent(&pr[kPfFinderCutNice], n_cut0); xw::atomic_add64_agent(&pr[kPfFinderCutTop], n_cut1);
-            xw::atomic_add64_agent(&pr[kPfFinderCutRkCand], n_cut2); xw::atomic_add64_agent(&pr[kPfFinderCutRkCatchUp], n_cut3); xw::atomic_add64_agent(&pr[kPfFinderCutOther], n_cut4);
-            xw::atomic_add64_agent(&pr[kPfFinderCutBin], n_cut5);
+            xw::atomic_add64_agent(&pr[kPfFinderBlocks], s_blocks); xw::atomic_add64_agent(&pr[kPfFinderCutNice], s_cut0); xw::atomic_add64_agent(&pr[kPfFinderCutTop], s_cut1);
+            xw::atomic_add64_agent(&pr[kPfFinderCutRkCand], s_cut2); xw::atomic_add64_agent(&pr[kPfFinderCutRkCatchUp], s_cut3); xw::atomic_add64_agent(&pr[kPfFinderCutOther], s_cut4);
+            xw::atomic_add64_agent(&pr[kPfFinderCutBin], s_cut5);
             xw::atomic_add64_agent(&pr[kPfFinderWait], t_wait); xw::atomic_add64_agent(&pr[kPfFinderTotal], xw::tick() - t_start); xw::atomic_add64_agent(&pr[kPfFinderWaitBt], t_wait_bt);
-            xw::atomic_add64_agent(&pr[kPfFinderLateUnc], n_late_unc); xw::atomic_add64_agent(&pr[kPfFinderLateOther], n_late_other);
-            xw::atomic_add64_agent(&pr[kPfRkShortTop], n_so_top); xw::atomic_add64_agent(&pr[kPfRkShortTie], n_so_tie); xw::atomic_add64_agent(&pr[kPfRkShortWon], n_so_won);
-            xw::atomic_add64_agent(&pr[kPfFinderSegOwn], n_seg_own); xw::atomic_add64_agent(&pr[kPfFinderSegWait], n_seg_wait);
-            xw::atomic_add64_agent(&pr[kPfFinderLateHot], n_late_hot); xw::atomic_add64_agent(&pr[kPfFinderLateFirst], n_late_first); xw::atomic_add64_agent(&pr[kPfFinderLateBlocks], n_late_blocks);
+            xw::atomic_add64_agent(&pr[kPfFinderLateUnc], s_late_unc); xw::atomic_add64_agent(&pr[kPfFinderLateOther], s_late_other);
+            xw::atomic_add64_agent(&pr[kPfRkShortTop], s_so_top); xw::atomic_add64_agent(&pr[kPfRkShortTie], s_so_tie); xw::atomic_add64_agent(&pr[kPfRkShortWon], s_so_won);
+            xw::atomic_add64_agent(&pr[kPfFinderSegOwn], s_seg_own); xw::atomic_add64_agent(&pr[kPfFinderSegWait], s_seg_wait);
+            xw::atomic_add64_agent(&pr[kPfFinderLateHot], s_late_hot); xw::atomic_add64_agent(&pr[kPfFinderLateFirst], s_late_first); xw::atomic_add64_agent(&pr[kPfFinderLateBlocks], s_late_blocks);
 #ifdef NLZM_PROFILE
             for (uint32_t z = 0; z < kPfFinderSecN; z++) xw::atomic_add64_agent(&pr[kPfFinderSec + z], t_f[z]);
 #endif
@@ -908,6 +927,7 @@ struct Finder {
 };
 
 
+// isa-region: table stage
 // =================================================================================================
 // table stage
 // =================================================================================================
@@ -1369,6 +1389,7 @@ XW_FN void Table::capture(uint32_t a, const unsigned long long *f, uint32_t fn)
 }
 
 
+// isa-region: parser and helper parsers
 // =================================================================================================
 // parser stage
 // =================================================================================================
