@@ -20,6 +20,7 @@
 
 #include "nlzm_host_state.h"
 #include "nlzm_report.h"
+#include "nlzm_stream_plan.h"
 
 #include "nlzm_launch.h"
 
@@ -76,6 +77,27 @@ void free_stream_buffers(Ctx &C)
     C.buf = StreamBuffers{}; C.set[0] = C.set[1] = LaunchSet{}; C.set_idx = 0;
     C.open = false;
 }
+void release_launch_stream(Ctx &C)
+{
+    for (auto &set : C.launch_ev) for (auto &ev : set) if (ev) { (void)hipEventDestroy(ev); ev = nullptr; }
+    if (C.launch_st) { (void)hipStreamDestroy(C.launch_st); C.launch_st = nullptr; }
+    if (C.launch_pack) { (void)hipHostFree(C.launch_pack); C.launch_pack = nullptr; }
+}
+namespace {
+// the bytes of one stream's entry of a pack (nlzm_launch.h)
+size_t pack_entry_bytes() { return (size_t)(stream2_pack_size() / stream2_pack_capacity()); }
+// what a single stream's persistent launches are queued on and bracketed with (Ctx::launch_st): made once per context, by the first stream that is opened on it
+int make_launch_stream(Ctx &C)
+{
+    if (C.launch_st) return 0;
+    int lo_p = 0, hi_p = 0;
+    HIPCHK(hipDeviceGetStreamPriorityRange(&lo_p, &hi_p));
+    HIPCHK(hipStreamCreateWithPriority(&C.launch_st, hipStreamNonBlocking, hi_p));
+    for (auto &set : C.launch_ev) for (auto &ev : set) HIPCHK(hipEventCreate(&ev));
+    HIPCHK(hipHostMalloc(&C.launch_pack, 2 * pack_entry_bytes(), hipHostMallocDefault));      // (one entry per launch set)
+    return 0;
+}
+}  // namespace
 void release_own_io(Ctx &C)
 {
     if (C.own_in) { (void)hipFree(C.own_in); C.own_in = nullptr; }
@@ -153,7 +175,7 @@ int alloc_launch_set(Ctx &C, LaunchSet &S)
         DEVALLOC(S.hot_of_bin, (size_t)K.nheads * 4);
         DEVALLOC(S.hot_list, ((size_t)K.hot_max + 1) * 4);
     }
-    if (K.in_set) DEVALLOC(S.snap, sizeof(v2::RoundSnap));
+    DEVALLOC(S.snap, sizeof(v2::RoundSnap));
     return 0;
 }
 }  // namespace
@@ -239,14 +261,18 @@ int stream_begin(Ctx &C, const Options &O, const void *d_src, uint64_t n, uint32
     for (int i = 0; i < 4; i++) P.rep[i] = (uint32_t)i + 1;                       // :1154-1158
     DEVFILL(hipMemcpyAsync(B.persist, &P, sizeof P, hipMemcpyHostToDevice, C.st));
 
-    if (!K.in_set) {    // the per-launch arrays take about 2.3 KB per position of a launch: a launch that does not fit is cut down
+    K.depth = 2;
+    if (!K.in_set) {    // the per-launch arrays take about 2.3 KB per position of a launch: a launch that does not fit is cut down, and the stream
+        // has a second launch set where that fits as well (nlzm_stream_plan.h)
         // (not for the streams of a block set: blocks_begin fitted their batch to the memory, and the free memory differs between the pass that
         //  measures what a stream takes and the pass that takes it -- the pool itself is allocated in between)
         size_t free_b = 0, total_b = 0;
         HIPCHK(hipMemGetInfo(&free_b, &total_b));
-        const double room = 0.6 * (double)free_b - 4.0 * (double)(1ull << K.t_bits);        // (the pre-filter table: up to 2^33 entries)
-        const double per_chunk = launch_bytes_per_chunk(g);
-        if (room > per_chunk && (double)K.batch * per_chunk > room) K.batch = (uint32_t)(room / per_chunk);
+        const stream_plan::Plan plan = stream_plan::make_plan((double)free_b, 4.0 * (double)(1ull << K.t_bits) /* the pre-filter table: up to 2^33 entries */,
+                                                              launch_bytes_per_chunk(g), K.batch, g.nchunks);
+        K.batch = plan.batch; K.depth = plan.depth;
+        const int rc = make_launch_stream(C);
+        if (rc) return rc;
     }
     // (RK256 hashes of ONE launch's positions -- the array is indexed by absolute position through a base pointer moved back by
     //  the launch's first hashed position, so only a launch's worth is ever resident: 4 B x (launch + lookahead) instead of 4 B
@@ -261,7 +287,7 @@ int stream_begin(Ctx &C, const Options &O, const void *d_src, uint64_t n, uint32
     DEVALLOC(B.scratch, K.batch * K.syms_stride * 4);
     DEVALLOC(B.frames, K.batch * K.frame_stride);
     DEVALLOC(B.dst_off, K.batch * sizeof(unsigned long long));
-    for (uint32_t s = 0; s < (K.in_set ? 2u : 1u); s++) { const int rc = alloc_launch_set(C, C.set[s]); if (rc) return rc; }
+    for (uint32_t s = 0; s < K.depth; s++) { const int rc = alloc_launch_set(C, C.set[s]); if (rc) return rc; }
 
     // pre-filter tables, per-launch hand-off arrays, bins
     for (;;) {      // (a device with less free memory than the table wants: a smaller table only marks more positions as undecided)
@@ -306,23 +332,36 @@ int stream_begin(Ctx &C, const Options &O, const void *d_src, uint64_t n, uint32
     return 0;
 }
 
+// The hot bins of a launch whose bins are made (step_pre).  From how many positions a bin counts as hot: a single stream's threshold follows the
+// pace of the launch before it (Options::hot_min), so this is queued when that launch has ended, in front of the launch itself.
+static void select_hot_bins(Ctx &C, const StepPlan &P, hipStream_t st)
+{
+    const StreamConfig &K = C.cfg;
+    const LaunchSet &L = C.set[P.set];
+    const unsigned long long lpos = (unsigned long long)K.batch * C.g.chunk_size;
+    // (the streams of a block set have a hundred heads to a lane: there a wave pays from positions / 480 on -- 112.6 -> 115.6 MB/s against 8,192)
+    const double by_pace = K.in_set ? (double)lpos / 480.0 : (C.last_launch_ms > 0 ? 24.0 * C.last_launch_ms : (double)lpos / 240.0);
+    const uint32_t hot_min = K.hot_min > 0 ? K.hot_min : (uint32_t)(by_pace < 512 ? 512 : (by_pace > 1e9 ? 1e9 : by_pace));
+    launch_hot_select(L.bin_off, P.nb, K.nheads, K.hot_max, hot_min, L.hot_of_bin, L.hot_list, C.buf.wcnt, st);
+}
+
 // One launch's worth of a stream, in three parts so that several streams can share ONE persistent launch:
 //   step_pre   pre-pass kernels and the hand-off arrays of chunks [c0, c1) on the stream's own HIP stream
 //   (launch)   pipeline_kernel for this stream alone, or pipeline_multi_kernel for a group of streams
 //   step_post  frame coder, frame lengths back to the host, checks, gather into the output
-// ahead: the launch before this one may still be on the device (block mode; the other launch set is made the current one, and
-// the progress words are set by round_open_kernel on the launch's own HIP stream instead of a copy here)
-int step_pre(Ctx &C, uint32_t todo, StepPlan &P, bool ahead)
+// The launch before this one may still be on the device: with two launch sets the other one is made the current one, and the progress
+// words are set by round_open_kernel on the launch's own HIP stream, not by a copy from here.
+int step_pre(Ctx &C, uint32_t todo, StepPlan &P)
 {
     const Geom &g = C.g;
     const StreamConfig &K = C.cfg;
     const StreamBuffers &B = C.buf;
-    if (ahead) { if (!K.in_set) return fail(NLZM_HIP_E_ARG, "no second launch set"); C.set_idx ^= 1; }
+    if (K.depth > 1) C.set_idx ^= 1;
     const LaunchSet &L = C.set[C.set_idx];
     const uint32_t c0 = C.pre_chunk, nb = todo < K.batch ? todo : K.batch, c1 = c0 + nb;
     C.pre_chunk = c1;
     P.c0 = c0; P.c1 = c1; P.nb = nb;
-    P.set = C.set_idx; P.ahead = ahead;
+    P.set = C.set_idx;
     hipEvent_t *ev = C.ev[P.set];
     Globals &G = P.G;
     memset(&G, 0, sizeof G);
@@ -363,20 +402,12 @@ int step_pre(Ctx &C, uint32_t todo, StepPlan &P, bool ahead)
                          B.pf_c1, L.unc, C.st);
         launch_bin(C.d_in, g, c0, nb, K.nheads, L.bin_off, B.bin_cur, L.bin_pos, L.unc, (uint32_t)a0, C.st);
         if (K.hot_max) {
-            const unsigned long long lpos = (unsigned long long)K.batch * g.chunk_size;
-            // (the streams of a block set have a hundred heads to a lane: there a wave pays from positions / 480 on -- 112.6 -> 115.6 MB/s against 8,192)
-            const double by_pace = K.in_set ? (double)lpos / 480.0 : (C.last_launch_ms > 0 ? 24.0 * C.last_launch_ms : (double)lpos / 240.0);
-            const uint32_t hot_min = K.hot_min > 0 ? K.hot_min : (uint32_t)(by_pace < 512 ? 512 : (by_pace > 1e9 ? 1e9 : by_pace));
-            launch_hot_select(L.bin_off, nb, K.nheads, K.hot_max, hot_min, L.hot_of_bin, L.hot_list, B.wcnt, C.st);
+            // (a single stream picks its hot bins by the pace of the launch before, which may still be on the device now: select_hot_bins is stream_step's to queue)
+            if (K.in_set) select_hot_bins(C, P, C.st);
             G.hot_of_bin = L.hot_of_bin; G.hot_list = L.hot_list; G.hot_undo = B.hot_undo;
         }
     }
-    {   // progress words of the stages: everything before the launch's first position is done
-        v2::Hx &h = C.hx_host;          // (lives until the copy has been made)
-        memset(&h, 0, sizeof h);
-        h.f_pos = h.t_pos = h.t_out = h.p_pos = (uint32_t)a0;
-        h.p_seg = ((unsigned long long)(uint32_t)a0 << 32) | (uint32_t)a0;
-        if (!ahead) HIPCHK(hipMemcpyAsync(B.v2_hx, &h, sizeof h, hipMemcpyHostToDevice, C.st));
+    {   // (the progress words of the stages -- everything before the launch's first position is done -- are round_open_kernel's to set)
         P.V.ft = B.v2_ft; P.V.tp = B.v2_tp; P.V.tf = B.v2_tf; P.V.hx = B.v2_hx; P.V.state = B.v2_state; P.V.hb = B.v2_hb;
         G.progress = &B.v2_hx->f_pos;
         G.test_fail = K.test_fail_launch >= 0 && (int64_t)C.v2_launch_no == K.test_fail_launch ? 1u : 0u;
@@ -386,7 +417,7 @@ int step_pre(Ctx &C, uint32_t todo, StepPlan &P, bool ahead)
     return 0;
 }
 
-// pipe_ms: time of the persistent launch when it was not this stream's own (group launch), else < 0
+// pipe_ms: time of the persistent launch between its own events (a group launch: 0, the set adds it up itself)
 // (in three parts, so that the streams of a block set have their frame coders and gathers in flight together: every part of
 //  every stream is queued before the next part waits for any of them)
 int step_post_issue(Ctx &C, const StepPlan &P)
@@ -396,19 +427,13 @@ int step_post_issue(Ctx &C, const StepPlan &P)
     hipEvent_t *ev = C.ev[P.set];
     const uint32_t nb = P.nb;
     C.post_hm.resize(nb); C.post_hoff.resize(nb);
-    C.post_aborted = 0;
     HIPCHK(hipEventRecord(ev[kEvLaunchEnd], C.st));
     launch_rans(L.syms, K.syms_stride, L.bits, K.bits_stride, L.fmeta, C.buf.scratch, K.syms_stride, C.buf.frames,
                 K.frame_stride, (uint32_t)K.frame_stride, nb, C.st);
     HIPCHK(hipEventRecord(ev[kEvCoderEnd], C.st));
     HIPCHK(hipMemcpyAsync(C.post_hm.data(), L.fmeta, nb * sizeof(FrameMeta), hipMemcpyDeviceToHost, C.st));
-    if (P.ahead) {          // (the stream's next launch may be running: the copy round_close_kernel made)
-        HIPCHK(hipMemcpyAsync(&C.post_snap, L.snap, sizeof(v2::RoundSnap), hipMemcpyDeviceToHost, C.st));
-        return 0;
-    }
-    HIPCHK(hipMemcpyAsync(&C.post_P, C.buf.persist, sizeof C.post_P, hipMemcpyDeviceToHost, C.st));
-    HIPCHK(hipMemcpyAsync(&C.post_aborted, L.abort_word, 4, hipMemcpyDeviceToHost, C.st));
-    HIPCHK(hipMemcpyAsync(&C.hx_host, C.buf.v2_hx, sizeof(v2::Hx), hipMemcpyDeviceToHost, C.st));
+    // (the stream's next launch may be running: the copy round_close_kernel made)
+    HIPCHK(hipMemcpyAsync(&C.post_snap, L.snap, sizeof(v2::RoundSnap), hipMemcpyDeviceToHost, C.st));
     return 0;
 }
 int step_post_check(Ctx &C, const StepPlan &P)
@@ -422,17 +447,16 @@ int step_post_check(Ctx &C, const StepPlan &P)
     std::vector<unsigned long long> &hoff = C.post_hoff;
     HIPCHK(hipStreamSynchronize(C.st));
     HIPCHK(hipGetLastError());
-    if (P.ahead) { C.post_P.error = C.post_snap.error; C.post_P.next_chunk = C.post_snap.next_chunk; C.post_aborted = C.post_snap.aborted; C.hx_host = C.post_snap.hx; }
-    const Persist &Pst = C.post_P;
-    const uint32_t aborted = C.post_aborted;
+    const v2::RoundSnap &Pst = C.post_snap;
+    const v2::Hx &h = Pst.hx;
+    const uint32_t aborted = Pst.aborted;
     float rk_ms = 0, pre_ms = 0;
     HIPCHK(hipEventElapsedTime(&rk_ms, ev[kEvRkBegin], ev[kEvRkEnd]));
     HIPCHK(hipEventElapsedTime(&pre_ms, ev[kEvRkEnd], ev[kEvPrepEnd]));
     C.tm.prep_ms += rk_ms + pre_ms; C.tm.prep_launches += 5; C.tm.total_ms += rk_ms + pre_ms;
     C.arena_out = false;
-    if (Pst.error || C.hx_host.err) {
+    if (Pst.error || h.err) {
         // the first error any stage raised, and where every stage was when it left (nlzm_v2.h: raise(), Hx::dbg)
-        const v2::Hx &h = C.hx_host;
         WorkerCounters wc{};
         (void)hipMemcpy(&wc, C.buf.wcnt, sizeof wc, hipMemcpyDeviceToHost);
         char where[kErrText];
@@ -440,7 +464,7 @@ int step_post_check(Ctx &C, const StepPlan &P)
         return fail(NLZM_HIP_E_KERNEL, "device error %u in chunks [%u,%u) (parser stopped at chunk %u): %s", Pst.error ? Pst.error : h.err, c0, c1, Pst.next_chunk, where);
     }
     // (the worker lanes drop a pair that finds no extension block and go on: the cursor says how many blocks were asked for)
-    C.arena_out = K.ext_cap && C.hx_host.ext_cur > K.ext_cap;
+    C.arena_out = K.ext_cap && h.ext_cur > K.ext_cap;
     if (C.arena_out) return fail(NLZM_HIP_E_KERNEL, "the extension arena of the BT4 pair lists (%u blocks per launch) was used up in chunks [%u,%u): more positions with over %u "
                                      "record-setters than a block set reserves for", K.ext_cap, c0, c1, K.pstride);
     if (aborted) return fail(NLZM_HIP_E_KERNEL, "worker lanes aborted (code %u) in chunks [%u,%u)", aborted, c0, c1);
@@ -476,7 +500,6 @@ int step_post_done(Ctx &C, const StepPlan &P, float pipe_ms)
     const uint32_t c1 = P.c1;
     HIPCHK(hipStreamSynchronize(C.st));
     float a = pipe_ms, b = 0, c = 0;
-    if (pipe_ms < 0) HIPCHK(hipEventElapsedTime(&a, ev[kEvLaunchBegin], ev[kEvLaunchEnd]));
     HIPCHK(hipEventElapsedTime(&b, ev[kEvLaunchEnd], ev[kEvCoderEnd]));
     HIPCHK(hipEventElapsedTime(&c, ev[kEvGatherBegin], ev[kEvGatherEnd]));
     C.tm.match_parse_ms += a; C.tm.match_parse_launches++;
@@ -487,31 +510,69 @@ int step_post_done(Ctx &C, const StepPlan &P, float pipe_ms)
     C.next_chunk = c1;
     return 0;
 }
-namespace {
-int step_post(Ctx &C, const StepPlan &P, float pipe_ms)
-{
-    int rc = step_post_issue(C, P);
-    if (!rc) rc = step_post_check(C, P);
-    if (!rc) rc = step_post_done(C, P, pipe_ms);
-    return rc;
-}
-}  // namespace
-
+// A call's launches follow one another without the device waiting for the host's work between them (StreamConfig::depth 2).  The pre-pass of
+// launch k + 1 is queued on the stream's HIP stream while launch k is on the device; when launch k has ended -- the hot bins of launch k + 1 are
+// picked by the pace of launch k, as they always were -- launch k + 1 goes on the launch stream at once, and only then are the frames of launch k
+// coded, copied and gathered, on the stream's HIP stream beside launch k + 1.  The per-stream buffers of the coder and the gather (scratch, frames,
+// dst_off) are used in that HIP stream's order: launch k + 1's coder follows launch k's gather.  A launch is bracketed by round_open_kernel and
+// round_close_kernel like a block set's: the progress words are set and copied aside on the device, and a launch queued behind a failed one -- the
+// host has not looked at launch k when it queues k + 1 -- leaves at once (the sticky Persist::error).  With depth 1 -- no room for a second launch
+// set -- every launch is collected before the next pre-pass is queued: the same loop.  Nothing stays queued when the call returns, whatever it returns.
 int stream_step(Ctx &C, uint32_t max_chunks, uint64_t *in_done, uint64_t *out_done, int *finished)
 {
     if (!C.open) return fail(NLZM_HIP_E_ARG, "no open stream");
+    if (!C.launch_st) return fail(NLZM_HIP_E_ARG, "the stream has no launch stream (a stream of a block set steps with its set)");
     const Geom &g = C.g;
     uint32_t todo = g.nchunks - C.next_chunk;
     if (max_chunks && todo > max_chunks) todo = max_chunks;
-    while (todo) {
-        StepPlan P;
-        int rc = step_pre(C, todo, P);
-        if (rc) return rc;
-        HIPCHK(hipEventRecord(C.ev[P.set][kEvLaunchBegin], C.st));
-        launch_pipeline2(g, P.G, P.V, P.c0, P.c1, C.cfg.worker_blocks, C.st);
-        rc = step_post(C, P, -1.0f);
-        if (rc) return rc;
-        todo -= P.nb;
+    StepPlan plan[2];
+    uint32_t head = 0, prepped = 0, launched = 0;       // of the launches plan[head & 1] ..: `prepped` have their pre-pass queued, the first `launched` of them the launch too
+    auto prepare = [&](StepPlan &P) -> int {
+        const int rc = step_pre(C, todo, P);
+        if (!rc) todo -= P.nb;
+        return rc;
+    };
+    auto launch = [&](const StepPlan &P) -> int {
+        hipEvent_t *lev = C.launch_ev[P.set];
+        void *pack = (uint8_t *)C.launch_pack + P.set * pack_entry_bytes();
+        fill_stream2_args(pack, 0, g, P.G, P.V, P.c0, P.c1, C.set[P.set].snap);
+        HIPCHK(hipStreamWaitEvent(C.launch_st, C.ev[P.set][kEvPrepEnd], 0));
+        if (C.cfg.hot_max) select_hot_bins(C, P, C.launch_st);
+        launch_round_open(pack, 1, C.launch_st);
+        HIPCHK(hipEventRecord(lev[0], C.launch_st));
+        launch_pipeline2(g, P.G, P.V, P.c0, P.c1, C.cfg.worker_blocks, C.launch_st);
+        HIPCHK(hipEventRecord(lev[1], C.launch_st));
+        launch_round_close(pack, 1, C.launch_st);
+        HIPCHK(hipEventRecord(lev[2], C.launch_st));
+        return 0;
+    };
+    auto ended = [&](const StepPlan &P, float &ms) -> int {         // waits for the launch itself, not for what is queued behind it
+        hipEvent_t *lev = C.launch_ev[P.set];
+        HIPCHK(hipEventSynchronize(lev[1]));
+        HIPCHK(hipEventElapsedTime(&ms, lev[0], lev[1]));
+        if (ms > 0) C.last_launch_ms = ms;
+        return 0;
+    };
+    auto collect = [&](const StepPlan &P) -> int {
+        HIPCHK(hipStreamWaitEvent(C.st, C.launch_ev[P.set][2], 0));
+        int rc = step_post_issue(C, P);
+        if (!rc) rc = step_post_check(C, P);
+        float ms = 0;
+        if (!rc) rc = ended(P, ms);
+        return rc ? rc : step_post_done(C, P, ms);
+    };
+    int rc = 0;
+    while (!rc && (todo || prepped)) {
+        while (!rc && todo && prepped < C.cfg.depth) { rc = prepare(plan[(head + prepped) & 1]); if (!rc) prepped++; }
+        if (!rc && !launched) { rc = launch(plan[head & 1]); launched = 1; }
+        if (!rc && prepped > 1) { float ms = 0; rc = ended(plan[head & 1], ms); if (!rc) rc = launch(plan[(head + 1) & 1]); launched = 2; }
+        if (!rc) { rc = collect(plan[head & 1]); head++; prepped--; launched--; }
+    }
+    if (rc) {       // (the text is the failing launch's; what is queued behind it is waited for -- every device wait is bounded -- and looked at by nobody)
+        (void)hipStreamSynchronize(C.launch_st);
+        (void)hipStreamSynchronize(C.st);
+        (void)hipGetLastError();
+        return rc;
     }
     if (in_done) {
         const unsigned long long d = (unsigned long long)C.next_chunk * g.chunk_size;
@@ -604,7 +665,7 @@ int dev_init(DevState &D, int device)
     C.device = device;
     C.cu_count = prop.multiProcessorCount;
     HIPCHK(hipStreamCreateWithFlags(&C.st, hipStreamNonBlocking));
-    for (auto &ev : C.ev[0]) HIPCHK(hipEventCreate(&ev));
+    for (auto &set : C.ev) for (auto &ev : set) HIPCHK(hipEventCreate(&ev));
     C.inited = true;
     return 0;
 }
@@ -619,7 +680,8 @@ void dev_shutdown(DevState &D)
     release_own_io(C);
     if (C.stage.cap_words) { (void)hipFree(C.stage.cap_words); C.stage.cap_words = nullptr; }
     if (C.stage.cap_used) { (void)hipFree(C.stage.cap_used); C.stage.cap_used = nullptr; }
-    for (auto &ev : C.ev[0]) if (ev) { (void)hipEventDestroy(ev); ev = nullptr; }
+    for (auto &set : C.ev) for (auto &ev : set) if (ev) { (void)hipEventDestroy(ev); ev = nullptr; }
+    release_launch_stream(C);
     if (C.st) { (void)hipStreamDestroy(C.st); C.st = nullptr; }
     C.inited = false;
 }

@@ -33,6 +33,7 @@ void block_ctx_destroy(Ctx &c)
 {
     free_stream_buffers(c);
     for (auto &set : c.ev) for (auto &ev : set) if (ev) { (void)hipEventDestroy(ev); ev = nullptr; }
+    release_launch_stream(c);           // (a stream that was made again as a single stream has one)
     if (c.st) { (void)hipStreamDestroy(c.st); c.st = nullptr; }
     c.inited = false;
 }
@@ -255,7 +256,7 @@ static int blocks_step_impl(DevState &D, uint32_t max_chunks_per_block, uint64_t
             if (todo[i]) act.push_back((uint32_t)i);
         }
         if (act.empty()) return 0;
-        for (uint32_t i : act) { const int rc = step_pre(D.jobs[i].c, todo[i], R.plan[q][i], true); if (rc) return rc; }
+        for (uint32_t i : act) { const int rc = step_pre(D.jobs[i].c, todo[i], R.plan[q][i]); if (rc) return rc; }
         uint8_t *ph = (uint8_t *)D.pack_host + (size_t)q * stream2_pack_size(), *pd = (uint8_t *)D.pack_dev + (size_t)q * stream2_pack_size();
         for (uint32_t k = 0; k < act.size(); k++) {
             Ctx &c = D.jobs[act[k]].c;

@@ -71,6 +71,8 @@ struct Options {
 struct StreamConfig {
     bool in_set = false;                    // a stream of a block set: buffers from the set's pool, two launch sets, short pair lists and an arena
     uint32_t batch = 0;                     // chunks per launch
+    uint32_t depth = 1;                     // launch sets: 2 -- the pre-pass and the launch of k + 1 are queued before launch k is collected (a block set's streams always;
+                                            // a single stream where a second set fits the device: nlzm_stream_plan.h)
     uint32_t worker_blocks = 0, worker_threads = 0;
     uint32_t nheads = 0;                    // bins: one per worker lane (or per head when there are fewer heads than lanes)
     uint32_t hot_max = 0;                   // waves that take a hot bin each, over all worker blocks (0: none)
@@ -85,15 +87,16 @@ struct StreamConfig {
     unsigned long long syms_stride = 0, bits_stride = 0, frame_stride = 0;
 };
 
-// Everything that exists once per launch set: what a pre-pass writes or a frame coder reads.  A single stream has one.  Block mode queues
-// launch k + 1 (and runs its pre-pass) while launch k is on the device and codes the frames of launch k while launch k + 1 is: a stream of
-// a block set has two, and a pre-pass that runs ahead makes the other one the current one (Ctx::set_idx).
+// Everything that exists once per launch set: what a pre-pass writes or a frame coder reads.  Launch k + 1 is queued (and its pre-pass runs) while
+// launch k is on the device, and the frames of launch k are coded while launch k + 1 is: a stream has two (StreamConfig::depth; a single stream
+// on a device too small for the second has one, and collects every launch before it queues the next), and a pre-pass makes the other one the
+// current one (Ctx::set_idx).
 struct LaunchSet {
     uint32_t *rkhash = nullptr, *bt_ready = nullptr, *bt_flag = nullptr, *abort_word = nullptr, *bin_off = nullptr, *bin_pos = nullptr,
              *hot_of_bin = nullptr, *hot_list = nullptr, *syms = nullptr;
     uint8_t *unc = nullptr, *bits = nullptr;
     FrameMeta *fmeta = nullptr;
-    v2::RoundSnap *snap = nullptr;          // (block mode) what round_close_kernel copies aside for the host
+    v2::RoundSnap *snap = nullptr;          // what round_close_kernel copies aside for the host
 };
 
 // The device buffers a stream has once, whatever the number of its launch sets.
@@ -115,7 +118,7 @@ struct StreamBuffers {
 };
 
 // the events of a launch set: what a step brackets with them, and two for a call's own timing (nlzm_hip_compress: upload and download; a block set's step: its device time)
-enum { kEvLaunchBegin, kEvLaunchEnd /* = frame coder begin */, kEvCoderEnd, kEvGatherBegin, kEvGatherEnd, kEvRkBegin, kEvRkEnd /* = rest of the pre-pass begin */, kEvPrepEnd,
+enum { kEvLaunchEnd /* = frame coder begin */, kEvCoderEnd, kEvGatherBegin, kEvGatherEnd, kEvRkBegin, kEvRkEnd /* = rest of the pre-pass begin */, kEvPrepEnd,
        kEvCallBegin, kEvCallEnd, kEvN };
 
 // Stage tests only: what nlzm_hip_find_matches and nlzm_hip_parse_emit (nlzm_hip_stage.cpp) set before they run a stream, and dev_shutdown frees.
@@ -131,7 +134,13 @@ struct Ctx {
     bool inited = false;
     int device = 0, cu_count = 0;
     hipStream_t st = nullptr;
-    hipEvent_t ev[2][kEvN] = {};             // per launch set (the second one's: block mode)
+    hipEvent_t ev[2][kEvN] = {};             // per launch set
+    // a single stream's persistent launches: a HIP stream of higher priority than `st`, i.e. a hardware queue apart from the pre-passes and frame coders
+    // that run beside them on `st`; per launch set the events launch begins / ends / its results are copied aside, and the launch's arguments as
+    // round_open_kernel and round_close_kernel read them: a pack of one entry in pinned host memory (made by stream_begin when first needed)
+    hipStream_t launch_st = nullptr;
+    hipEvent_t launch_ev[2][3] = {};
+    void *launch_pack = nullptr;
     Pool *pool = nullptr;                   // (block mode) where the stream's buffers come from
 
     // the open stream
@@ -155,10 +164,9 @@ struct Ctx {
 
     StageCapture stage;                     // (stage tests)
 
-    // run state: what the step's frame coder has reported (step_post_issue .. _done), the progress words on their way to or from the device,
-    // timing.  Asynchronous copies read and write these: they stay where they are while the stream is open.
-    v2::Hx hx_host;
-    std::vector<FrameMeta> post_hm; std::vector<unsigned long long> post_hoff; Persist post_P; uint32_t post_aborted = 0; unsigned long long post_pos = 0;
+    // run state: what the step's frame coder has reported (step_post_issue .. _done), what round_close_kernel copied aside of the launch (the progress
+    // words among it), timing.  Asynchronous copies write these: they stay where they are while the stream is open.
+    std::vector<FrameMeta> post_hm; std::vector<unsigned long long> post_hoff; unsigned long long post_pos = 0;
     v2::RoundSnap post_snap;
     double last_launch_ms = 0;              // duration of the stream's last persistent launch (0: none yet)
     bool arena_out = false;                 // the last step_post_check failed because the launch used its pair-list arena up (block mode makes the stream again by itself)
@@ -199,7 +207,6 @@ template <class T> int dev_alloc(Ctx &C, T **p, size_t bytes)
 struct StepPlan {
     uint32_t c0 = 0, c1 = 0, nb = 0; Globals G; v2::GlobalsV2 V;
     uint32_t set = 0;
-    bool ahead = false;                         // the launch is followed by round_close_kernel: the host reads the set's `snap`
 };
 
 struct BlockJob {
@@ -277,13 +284,14 @@ bool prefilter_is_bitmap(const Geom &g);
 size_t prefilter_bytes(uint32_t t_bits, bool bitmap);
 double launch_bytes_per_chunk(const Geom &g);
 int stream_begin(Ctx &C, const Options &O, const void *d_src, uint64_t n, uint32_t hist_bits_req, void *d_dst, uint64_t dst_cap);
-int step_pre(Ctx &C, uint32_t todo, StepPlan &P, bool ahead = false);
+int step_pre(Ctx &C, uint32_t todo, StepPlan &P);
 int step_post_issue(Ctx &C, const StepPlan &P);
 int step_post_check(Ctx &C, const StepPlan &P);
 int step_post_done(Ctx &C, const StepPlan &P, float pipe_ms);
 int stream_step(Ctx &C, uint32_t max_chunks, uint64_t *in_done, uint64_t *out_done, int *finished);
 int stream_finish(Ctx &C, uint64_t *dst_len, bool report);
 void free_stream_buffers(Ctx &C);
+void release_launch_stream(Ctx &C);
 int alloc_own_io(Ctx &C, uint64_t n, uint64_t bound);
 void release_own_io(Ctx &C);
 // nlzm_hip_blocks.cpp
