@@ -195,6 +195,45 @@ uint64_t nlzm_hip_compress_blocks_bound(uint64_t n, uint32_t nblocks);
 int nlzm_hip_compress_blocks(const uint8_t *src, uint64_t n, uint32_t nblocks, uint32_t hist_bits_req,
                              uint8_t *dst, uint64_t dst_cap, uint64_t *block_len, uint64_t *dst_len);
 
+/* ---- blocks of the caller's choosing -------------------------------------------------------------------------- */
+/* k ranges of ONE buffer, each compressed as a stream of its own: range i is [off[i], off[i] + len[i]) of the n bytes at d_src (records, the files of
+ * an archive, tensors, pages -- or the blocks nlzm_hip_cut_points* finds).  k: 1 .. 65536.  off / len / block_len: host arrays of k entries.  Ranges
+ * may be empty, overlap, repeat and come in any order (the idiom of nlzm_hip_crc32_ranges and nlzm_hip_read_ranges).  Stream i is byte for byte the
+ * reference run on those bytes at hist_bits_req (encode_file, NLZM.cpp:1711), with the geometry of that range's own length, as an equal block's is; the
+ * streams are written back to back in the caller's order and block_len[i] (may be NULL) holds their lengths: a block container that every read-side
+ * entry point takes, with raw lengths len[i].  d_src needs the 128 readable bytes behind n that nlzm_hip_compress_blocks_dev asks for.
+ * Errors, all before any launch: a range with len > n - off is NLZM_HIP_E_ARG (the text names it); dst_cap below
+ * nlzm_hip_compress_ranges_bound(k, len) is NLZM_HIP_E_CAPACITY.  A call that fails leaves nothing open.
+ * Up to the device's capacity (64 on an MI355X) the ranges run as ONE block set, sized by its longest range: it opens wherever the equal split of
+ * count x longest bytes would.  More ranges run in sets of consecutive ranges, split as nlzm_hip_compress_blocks_dev splits its blocks ("container_set_blocks";
+ * 65 by 32: 22 + 22 + 21), one after another; "container_sets" counts them, nlzm_hip_get_stats sums over them.  No kernel differs from the equal split's. */
+int nlzm_hip_compress_ranges_dev(const void *d_src, uint64_t n, uint32_t k, const uint64_t *off, const uint64_t *len,
+                                 uint32_t hist_bits_req, void *d_dst, uint64_t dst_cap, uint64_t *block_len, uint64_t *dst_len);
+/* the same on host buffers (the 128 bytes behind the input are the library's; dst_cap is held to the same bound) */
+int nlzm_hip_compress_ranges(const uint8_t *src, uint64_t n, uint32_t k, const uint64_t *off, const uint64_t *len,
+                             uint32_t hist_bits_req, uint8_t *dst, uint64_t dst_cap, uint64_t *block_len, uint64_t *dst_len);
+/* Room the streams of k ranges of these lengths take at most: the sum of nlzm_hip_compress_bound(len[i]).  Needs no device.  0 when k is 0 or above
+ * 65536, or when the sum does not fit 64 bits. */
+uint64_t nlzm_hip_compress_ranges_bound(uint32_t k, const uint64_t *len);
+
+/* ---- content-defined cut points ----------------------------------------------------------------------------------- */
+/* Where to cut n bytes into blocks so that the cuts follow the content: an insertion or deletion moves the cuts around it and leaves the blocks
+ * further on as they were (byte for byte, so their streams and CRC32s too), which the equal partition cannot.  The rule (nlzm_amd/csrc/nlzm_cut.h;
+ * tests/cut_model.py restates it): G[b] = the upper 32 bits of splitmix64(b); h(p) = sum over j = 0 .. 31 of G[x[p - j]] << j modulo 2^32 for p >= 31
+ * (the gear hash h = (h << 1) + G[byte]); p is a candidate when the top avg_bits bits of h(p) are zero, its boundary p + 1.  From s = 0, while
+ * n - s > min_len: e = the first candidate boundary in [s + min_len, min(s + max_len, n)], else that upper end; stop if e >= n; cut[i++] = e; s = e.
+ * The blocks are the pieces between the cuts: all but the last hold min_len .. max_len bytes, 2^avg_bits on average beyond min_len where the
+ * content is varied; n = 0 has no cut (one empty block).  cut: a host array of cut_cap entries, ascending; *ncuts: how many were written.  More
+ * cuts than cut_cap: NLZM_HIP_E_CAPACITY, *ncuts the number needed, nothing written to cut.  Checked without a device or a launch: avg_bits 1 .. 30,
+ * 32 <= min_len <= max_len <= 2^31.  Reads stay inside [d_src, d_src + n): no padding, no alignment is asked for.
+ * On the device: one wave per segment of nlzm_hip_get_counter("cut_segment_bytes") bytes hashes every position and marks the candidates in a
+ * bitmap, then one wave walks the rule over the bitmap; device memory n / 8 bytes, a word per segment and the list; only the list comes back.
+ * Counters of the last call: "cut_us" (device time of both launches), "cut_candidates", "cut_segment_bytes" (needs no device). */
+int nlzm_hip_cut_points_dev(const void *d_src, uint64_t n, uint32_t avg_bits, uint64_t min_len, uint64_t max_len,
+                            uint64_t *cut, uint32_t cut_cap, uint32_t *ncuts);
+int nlzm_hip_cut_points(const uint8_t *src, uint64_t n, uint32_t avg_bits, uint64_t min_len, uint64_t max_len,
+                        uint64_t *cut, uint32_t cut_cap, uint32_t *ncuts);         /* uploads first */
+
 /* ---- streaming host input and output ---------------------- */
 /* The reference reads its input and writes its frames as it goes (NLZM.cpp:1774-1778, :1853, :1870-1885).  Here the
  * caller announces the input's length, hands the bytes over in pieces, in order (any piece size; a piece travels through

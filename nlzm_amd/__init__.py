@@ -37,6 +37,7 @@ ABI_SYMBOLS = [
     "nlzm_hip_read_ranges_dev", "nlzm_hip_read_ranges",
     "nlzm_hip_decode_begin_dev", "nlzm_hip_decode_begin", "nlzm_hip_decode_step", "nlzm_hip_decode_extend_dev", "nlzm_hip_decode_fetch",
     "nlzm_hip_decode_finish", "nlzm_hip_decode_abandon",
+    "nlzm_hip_compress_ranges_dev", "nlzm_hip_compress_ranges", "nlzm_hip_compress_ranges_bound", "nlzm_hip_cut_points_dev", "nlzm_hip_cut_points",
 ]
 DECODE_MORE = 1          # NLZM_HIP_DECODE_MORE
 TO_THE_END = (1 << 64) - 1
@@ -149,6 +150,13 @@ def load_library() -> C.CDLL:
         lib.nlzm_hip_decode_fetch.argtypes = [C.c_uint64, C.c_uint64, C.c_void_p]
         lib.nlzm_hip_decode_finish.argtypes = [u64p, u64p]
         lib.nlzm_hip_decode_abandon.restype = None
+    if hasattr(lib, "nlzm_hip_compress_ranges"):   # (absent from older diagnostic builds loaded through NLZM_LIB)
+        lib.nlzm_hip_compress_ranges_dev.argtypes = [C.c_void_p, C.c_uint64, C.c_uint32, u64p, u64p, C.c_uint32, C.c_void_p, C.c_uint64, u64p, u64p]
+        lib.nlzm_hip_compress_ranges.argtypes = [C.c_void_p, C.c_uint64, C.c_uint32, u64p, u64p, C.c_uint32, C.c_void_p, C.c_uint64, u64p, u64p]
+        lib.nlzm_hip_compress_ranges_bound.argtypes = [C.c_uint32, u64p]
+        lib.nlzm_hip_compress_ranges_bound.restype = C.c_uint64
+        lib.nlzm_hip_cut_points_dev.argtypes = [C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint64, C.c_uint64, u64p, C.c_uint32, u32p]
+        lib.nlzm_hip_cut_points.argtypes = [C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint64, C.c_uint64, u64p, C.c_uint32, u32p]
     _lib = lib
     return lib
 
@@ -209,6 +217,52 @@ def compress_blocks(data, nblocks: int, hist_bits: int = 22) -> list[bytes]:
         pos += int(lens[i])
     assert pos == out_len.value
     return out
+
+
+def compress_ranges(data, ranges, hist_bits: int = 22) -> list[bytes]:
+    """One stream per (offset, length) range of `data`, all in one call: the ranges may be empty, overlap, repeat and come in any order; stream i
+    is the reference's encode_file (NLZM.cpp:1711) run on data[off:off + length].  Up to a launch's capacity (64 on an MI355X) they are one block
+    set, more of them run in sets of consecutive ranges (counter "container_sets")."""
+    lib = load_library()
+    src = _bytes_in(data)
+    n, k = int(src.size), len(ranges)
+    if not 1 <= k <= 65536:
+        raise ValueError("ranges: 1 to 65536")
+    off, ln = (C.c_uint64 * k)(*[int(o) for o, _ in ranges]), (C.c_uint64 * k)(*[int(l) for _, l in ranges])
+    cap = int(lib.nlzm_hip_compress_ranges_bound(k, ln))
+    dst = np.empty(max(1, cap), dtype=np.uint8)
+    lens = (C.c_uint64 * k)()
+    out_len = C.c_uint64(0)
+    _chk(lib.nlzm_hip_compress_ranges(src.ctypes.data if n else None, n, k, off, ln, hist_bits, dst.ctypes.data, cap, lens, C.byref(out_len)))
+    out, pos = [], 0
+    for i in range(k):
+        out.append(dst[pos: pos + int(lens[i])].tobytes())
+        pos += int(lens[i])
+    assert pos == out_len.value
+    return out
+
+
+def cut_points(data, avg_bits: int, min_len=None, max_len=None) -> list[int]:
+    """Content-defined cut points of `data`, found on the device (nlzm_hip_cut_points; the rule: tests/cut_model.py): ascending offsets inside
+    (0, len(data)); blocks of 2^avg_bits bytes on average, min_len (default 2^(avg_bits - 2), 32 at least) to max_len (default 2^(avg_bits + 2))."""
+    lib = load_library()
+    src = _bytes_in(data)
+    n = int(src.size)
+    lo = max(32, 1 << max(0, avg_bits - 2)) if min_len is None else int(min_len)
+    hi = max(lo, min(1 << 31, 1 << (avg_bits + 2))) if max_len is None else int(max_len)
+    cap = min(n // max(lo, 1), 0xFFFFFFFF) if lo > 0 else 0
+    cuts = (C.c_uint64 * max(1, cap))()
+    got = C.c_uint32(0)
+    _chk(lib.nlzm_hip_cut_points(src.ctypes.data if n else None, n, avg_bits, lo, hi, cuts, cap, C.byref(got)))
+    return [int(cuts[i]) for i in range(got.value)]
+
+
+def cut_ranges(n: int, cuts) -> list[tuple[int, int]]:
+    """The (offset, length) blocks that the ascending cut points `cuts` make of n bytes: len(cuts) + 1 of them, back to back."""
+    edges = [0] + [int(c) for c in cuts] + [int(n)]
+    if any(b < a for a, b in zip(edges, edges[1:])):
+        raise ValueError("cuts: ascending offsets within the input")
+    return [(a, b - a) for a, b in zip(edges, edges[1:])]
 
 
 def compress_fed(data, hist_bits: int = 22, piece: int = 1 << 20) -> bytes:

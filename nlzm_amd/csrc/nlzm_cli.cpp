@@ -264,6 +264,7 @@ int main(int argc, char **argv)
     bool verify = false;                            // -verify (not in the reference): c decodes what it wrote on the device and compares it with the input
     bool with_crc = false;                          // -crc (not in the reference): c keeps every block's CRC32, hashed on the device, in the index (NLZMIDX 2); d / t check them
     bool on_gpu = false;                            // -gpu (not in the reference): d / t decode on the device; without it they are host-only and need none
+    uint32_t cdc_bits = 0;                          // -cdc:B (not in the reference): c cuts the blocks by content on the device, 2^B bytes a block on average
     uint32_t steps_k = 0;                           // -steps:K (not in the reference): d -gpu / t -gpu decode in steps of K frames per block
     std::vector<ByteRange> ranges;                  // -range:off:len (not in the reference): what x writes, in this order
     while (argc >= 2 && *argv[1] == '-') {
@@ -283,6 +284,14 @@ int main(int argc, char **argv)
             const int v = atoi(arg + 5);
             ngpus = (uint32_t)(v < 1 ? 1 : (v > 64 ? 64 : v));
             printf("GPUs: %d\n", ngpus);
+        } else if (!strncmp(arg, "cdc:", 4)) {
+            // digits and nothing else, 10 .. 30
+            unsigned v = 0;
+            const char *p = arg + 4;
+            bool ok = *p >= '0' && *p <= '9';
+            for (; ok && *p >= '0' && *p <= '9'; p++) { v = v * 10 + (unsigned)(*p - '0'); if (v > 30) ok = false; }
+            if (!ok || *p || v < 10) { printf("Error: -cdc:B takes B from 10 to 30 (blocks of 2^B bytes on average)\n"); return -1; }
+            cdc_bits = v;
         } else if (!strcmp(arg, "verify")) {
             verify = true;
         } else if (!strcmp(arg, "crc")) {
@@ -317,11 +326,12 @@ int main(int argc, char **argv)
         }
     }
     const int cmd = argc >= 2 ? (argv[1][0] | 0x20) : 0;
+    if (cdc_bits && (nblocks > 1 || ngpus)) { printf("Error: -cdc:B cuts the blocks by content; it does not go together with -blocks:k or -gpus:g\n"); return -1; }
     if (ngpus && nblocks > 64) { nblocks = 64; printf("Blocks: %d (on each GPU: a launch holds no more)\n", nblocks); }
     if (steps_k && !(on_gpu && ((argc == 4 && cmd == 'd') || (argc == 3 && cmd == 't')))) { printf("Error: -steps:K is for d -gpu and t -gpu\n"); return -1; }
     if (argc == 4 && cmd == 'c') {
         if (FILE *probe = fopen(argv[3], "rb")) { printf("Error: %s already exists\n", argv[3]); fclose(probe); return -1; }
-        const bool one_stream = !ngpus && nblocks == 1 && !verify;      // (-verify needs input and stream whole: the one-call path)
+        const bool one_stream = !ngpus && nblocks == 1 && !verify && !cdc_bits;      // (-verify and -cdc need the input whole: the one-call path)
         std::vector<uint8_t> in;
         FILE *fin = nullptr;
         uint64_t in_size = 0;
@@ -338,7 +348,30 @@ int main(int argc, char **argv)
         FILE *fout = fopen(argv[3], "wb");
         if (!fout) { printf("Error: %s file does not exist\n", argv[3]); if (fin) fclose(fin); return -1; }
         if (!ngpus && nlzm_hip_init(0)) { printf("Error: %s\n", nlzm_hip_last_error()); fclose(fout); remove(argv[3]); return -1; }
-        const uint32_t nstreams = ngpus ? ngpus * nblocks : nblocks;
+        uint32_t nstreams = ngpus ? ngpus * nblocks : nblocks;
+        std::vector<uint64_t> boff, braw;           // every block's bytes of the input: cut by content, or the equal partition
+        if (cdc_bits) {
+            // the cut points from the device, with the default lengths: 2^(B - 2) .. 2^(B + 2) bytes a block (2^31 at most)
+            const uint64_t min_len = 1ull << (cdc_bits - 2), max_len = cdc_bits + 2 > 31 ? 1ull << 31 : 1ull << (cdc_bits + 2);
+            std::vector<uint64_t> cuts(nlzm::container::kMaxBlocks - 1);
+            uint32_t ncuts = 0;
+            const int crc = nlzm_hip_cut_points(in.data(), in.size(), cdc_bits, min_len, max_len, cuts.data(), (uint32_t)cuts.size(), &ncuts);
+            if (crc == NLZM_HIP_E_CAPACITY) printf("Error: -cdc:%u cuts this input into %" PRIu64 " blocks, a container holds %u at most: raise B\n", cdc_bits, (uint64_t)ncuts + 1, nlzm::container::kMaxBlocks);
+            else if (crc) printf("Error: %s\n", nlzm_hip_last_error());
+            if (crc) { fclose(fout); remove(argv[3]); return -1; }
+            nstreams = ncuts + 1;
+            for (uint32_t i = 0; i < nstreams; i++) {
+                const uint64_t lo = i ? cuts[i - 1] : 0, hi = i < ncuts ? cuts[i] : (uint64_t)in.size();
+                boff.push_back(lo); braw.push_back(hi - lo);
+            }
+            printf("Blocks: %u (cut by content)\n", nstreams);
+        } else if (!one_stream) {
+            const uint64_t per = (in.size() + nstreams - 1) / nstreams;
+            for (uint32_t i = 0; i < nstreams; i++) {
+                const uint64_t lo = (uint64_t)i * per < in.size() ? (uint64_t)i * per : in.size(), hi = lo + per < in.size() ? lo + per : in.size();
+                boff.push_back(lo); braw.push_back(hi - lo);
+            }
+        }
         uint32_t hb, fb, cs, feed;
         nlzm_hip_geometry(in_size, hist_bits, &hb, &fb, &cs, &feed);
         {   // the reference's summary (:1755-1759): sizes of its own structures for this window
@@ -401,13 +434,15 @@ int main(int argc, char **argv)
             return 0;
         }
         // room for the streams (a guaranteed bound: 9.7 GB at 65,536 blocks).  Not a vector: nothing is filled, and the pages behind the streams' end are never touched
-        const size_t out_room = ngpus ? (size_t)nlzm_hip_compress_bound(in.size()) + (size_t)nstreams * (16 + 131072) : (size_t)nlzm_hip_compress_blocks_bound(in.size(), nblocks);
+        const size_t out_room = ngpus ? (size_t)nlzm_hip_compress_bound(in.size()) + (size_t)nstreams * (16 + 131072)
+                              : cdc_bits ? (size_t)nlzm_hip_compress_ranges_bound(nstreams, braw.data()) : (size_t)nlzm_hip_compress_blocks_bound(in.size(), nblocks);
         struct Room { uint8_t *p; size_t n; uint8_t *data() const { return p; } size_t size() const { return n; } ~Room() { free(p); } } out{ (uint8_t *)malloc(out_room ? out_room : 1), out_room };
         if (!out.data()) { printf("Error: no memory for %zu bytes of output\n", out_room); fclose(fout); remove(argv[3]); return -1; }
         std::vector<uint64_t> blen(nstreams);
         std::vector<int> devs;
         for (uint32_t d = 0; d < ngpus; d++) devs.push_back((int)d);
-        const int rc = ngpus ? nlzm_hip_compress_blocks_multi(devs.data(), ngpus, nblocks, in.data(), in.size(), hist_bits, out.data(), out.size(), blen.data(), &out_n)
+        const int rc = cdc_bits ? nlzm_hip_compress_ranges(in.data(), in.size(), nstreams, boff.data(), braw.data(), hist_bits, out.data(), out.size(), blen.data(), &out_n)
+                     : ngpus ? nlzm_hip_compress_blocks_multi(devs.data(), ngpus, nblocks, in.data(), in.size(), hist_bits, out.data(), out.size(), blen.data(), &out_n)
                      : nblocks > 1 ? nlzm_hip_compress_blocks(in.data(), in.size(), nblocks, hist_bits, out.data(), out.size(), blen.data(), &out_n)
                                    : nlzm_hip_compress(in.data(), in.size(), hist_bits, out.data(), out.size(), &out_n);
         clock_gettime(CLOCK_MONOTONIC, &w1);
@@ -437,12 +472,6 @@ int main(int argc, char **argv)
         std::vector<uint32_t> bcrc(nstreams, 0);
         uint32_t whole = 0;
         if (with_crc) {
-            std::vector<uint64_t> boff(nstreams), braw(nstreams);
-            const uint64_t per = (in.size() + nstreams - 1) / nstreams;
-            for (uint32_t i = 0; i < nstreams; i++) {
-                const uint64_t lo = (uint64_t)i * per < in.size() ? (uint64_t)i * per : in.size(), hi = lo + per < in.size() ? lo + per : in.size();
-                boff[i] = lo; braw[i] = hi - lo;
-            }
             int crc_rc = ngpus ? nlzm_hip_init(0) : 0;
             if (!crc_rc) crc_rc = nlzm_hip_crc32_ranges(in.data(), in.size(), nstreams, boff.data(), braw.data(), bcrc.data());
             if (crc_rc) { printf("Error: crc: %s\n", nlzm_hip_last_error()); fclose(fout); remove(argv[3]); return -1; }
@@ -450,7 +479,7 @@ int main(int argc, char **argv)
         }
         fwrite(out.data(), 1, (size_t)out_n, fout);
         fclose(fout);
-        if (nstreams > 1 || with_crc) {
+        if (nstreams > 1 || with_crc || cdc_bits) {
             // the block index, a sidecar: where every block's stream starts, how long it is and how many input bytes it holds.  The
             // streams stay self-delimiting -- the index only saves d/t the hop over every frame header of every block before the parallel decode can
             // start, and keeps the later blocks' boundaries when the container is damaged inside an earlier one.
@@ -458,12 +487,10 @@ int main(int argc, char **argv)
             if (FILE *fi = fopen(ip.c_str(), "wb")) {
                 if (with_crc) fprintf(fi, "NLZMIDX 2 %u %" PRIu64 " %" PRIu64 " %08X\n", nstreams, (uint64_t)in.size(), out_n, whole);
                 else fprintf(fi, "NLZMIDX 1 %u %" PRIu64 " %" PRIu64 "\n", nstreams, (uint64_t)in.size(), out_n);
-                const uint64_t per = (in.size() + nstreams - 1) / nstreams;
                 uint64_t off = 0;
-                for (uint32_t i = 0; i < nstreams; i++) {
-                    const uint64_t lo = (uint64_t)i * per < in.size() ? (uint64_t)i * per : in.size(), hi = lo + per < in.size() ? lo + per : in.size();
-                    if (with_crc) fprintf(fi, "%" PRIu64 " %" PRIu64 " %" PRIu64 " %08X\n", off, blen[i], hi - lo, bcrc[i]);
-                    else fprintf(fi, "%" PRIu64 " %" PRIu64 " %" PRIu64 "\n", off, blen[i], hi - lo);
+                for (uint32_t i = 0; i < nstreams; i++) {       // (each block's raw length its true one: the equal partition's, or the content's)
+                    if (with_crc) fprintf(fi, "%" PRIu64 " %" PRIu64 " %" PRIu64 " %08X\n", off, blen[i], braw[i], bcrc[i]);
+                    else fprintf(fi, "%" PRIu64 " %" PRIu64 " %" PRIu64 "\n", off, blen[i], braw[i]);
                     off += blen[i];
                 }
                 fclose(fi);
@@ -733,6 +760,7 @@ int main(int argc, char **argv)
                "\t-window:bits = Maximum window size in bits, default 22 (4 MB), min 15, max 28 (32 KB to 256 MB)\n"
                "\t-blocks:k = (this build) compress k independent blocks, 1 to 65536: as many at once as a launch holds (64), more of them\n"
                "\t            in sets one after another; d/t read the streams back to back\n"
+               "\t-cdc:B = (this build) c cuts the blocks by content on the GPU, 2^B bytes on average (B 10 to 30): an edit changes the blocks around it only\n"
                "\t-gpus:g = (this build) the blocks on GPUs 0..g-1 of this node, -blocks:k of them on each (64 at most)\n"
                "\t-verify = (this build) c decodes what it wrote on the GPU, one workgroup per stream, compares it with the input\n"
                "\t          and removes the output if they differ\n"

@@ -3,6 +3,8 @@
 // tests/host_sim/container_plan_sim.cpp include this one text, so that what the test proves is what the library runs:
 //   container::block_range   block i of the ceil(n / nblocks) partition (nlzm_amd/shard.py block_range, nlzm_hip_blocks_begin; a device's part of a multi-GPU call)
 //   container::make_plan     the sets: which blocks in which set, each set's byte range, the bound of what the whole container may take
+//   container::make_ranges_plan   the same for blocks that are ranges of the caller's choosing (nlzm_hip_compress_ranges*; the CPU harness
+//                            tests/host_sim/ranges_plan_sim.cpp): the ranges checked against the input, the sets, each set's longest range, the bound
 // The sets run one after another, each through the block-set code with the partition fixed to `per` bytes a block; a set's streams go straight
 // behind those of the set before it.  Standard library only; compiles with plain g++ -std=c++17.
 #pragma once
@@ -70,6 +72,63 @@ inline int make_plan(Plan &P, uint64_t n, uint32_t nblocks, uint32_t set_blocks,
         const uint64_t b = bound(len);
         if (b > ~0ull - P.out_bound) return plan_error(err, NLZM_HIP_E_ARG, "the blocks' bounds do not sum in 64 bits");
         P.out_bound += b;
+    }
+    return 0;
+}
+
+// ---- ranges of the caller's choosing (nlzm_hip_compress_ranges*) ----
+// Range i is [off[i], off[i] + len[i]) of n bytes: empty, overlapping, repeated, in any order.  The sets are consecutive ranges, split by the
+// same rule as make_plan's (k <= capacity: ONE set); a set's streams share the decisions of its LONGEST range, as the equal split's share those of `per`.
+struct RangeSet {
+    uint32_t first = 0, count = 0;                  // ranges [first, first + count)
+    uint64_t longest = 0;                           // the longest of them
+};
+struct RangesPlan {
+    uint32_t k = 0;
+    std::vector<RangeSet> sets;                     // in the caller's order
+    uint64_t out_bound = 0;                         // sum of bound(len[i]): what the streams can take at most
+    uint32_t bad_range = ~0u;                       // the range that runs over n, when that is the error
+};
+
+// the sum of bound(len[i]) over k ranges; false: k out of range, or the sum does not fit 64 bits
+template <class Bound>
+inline bool ranges_bound(uint32_t k, const uint64_t *len, Bound bound, uint64_t &sum)
+{
+    sum = 0;
+    if (!k || k > kMaxBlocks || !len) return false;
+    for (uint32_t i = 0; i < k; i++) {
+        const uint64_t b = bound(len[i]);
+        if (b > ~0ull - sum) return false;
+        sum += b;
+    }
+    return true;
+}
+
+template <class Bound>
+inline int make_ranges_plan(RangesPlan &P, uint64_t n, uint32_t k, const uint64_t *off, const uint64_t *len, uint32_t set_blocks, uint32_t capacity, Bound bound, ErrText err)
+{
+    P = RangesPlan{};
+    if (!k || k > kMaxBlocks) return plan_error(err, NLZM_HIP_E_ARG, "%u ranges: 1 .. %u in one call", k, kMaxBlocks);
+    if (!off || !len) return plan_error(err, NLZM_HIP_E_ARG, "null argument");
+    if (!capacity) return plan_error(err, NLZM_HIP_E_ARG, "the device holds no block set");
+    if (!set_blocks || set_blocks > capacity) return plan_error(err, NLZM_HIP_E_ARG, "container_set_blocks %u out of range (1 .. %u)", set_blocks, capacity);
+    for (uint32_t i = 0; i < k; i++)
+        if (off[i] > n || len[i] > n - off[i]) {    // (no off + len: it can wrap)
+            P.bad_range = i;
+            return plan_error(err, NLZM_HIP_E_ARG, "range %u (offset %llu, %llu bytes) runs over the %llu bytes of the input", i, (unsigned long long)off[i],
+                              (unsigned long long)len[i], (unsigned long long)n);
+        }
+    if (!ranges_bound(k, len, bound, P.out_bound)) return plan_error(err, NLZM_HIP_E_ARG, "the ranges' bounds do not sum in 64 bits");
+    P.k = k;
+    const uint32_t nsets = k <= capacity ? 1u : k / set_blocks + (k % set_blocks ? 1u : 0u);
+    const uint32_t base = k / nsets, more = k % nsets;
+    P.sets.resize(nsets);
+    uint32_t at = 0;
+    for (uint32_t s = 0; s < nsets; s++) {
+        RangeSet &S = P.sets[s];
+        S.first = at; S.count = base + (s < more ? 1u : 0u);
+        for (uint32_t i = S.first; i < S.first + S.count; i++) if (len[i] > S.longest) S.longest = len[i];
+        at += S.count;
     }
     return 0;
 }

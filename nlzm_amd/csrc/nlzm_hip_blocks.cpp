@@ -125,8 +125,14 @@ int nlzm_hip_blocks_begin(const void *d_src, uint64_t n, uint32_t nblocks, uint3
     DevState &D = cur();
     Ctx &C = D.ctx;
     const Options &O = D.opt;
-    const uint64_t per_fixed = D.blocks_per;        // (a multi-device call fixes the partition; cleared here)
+    uint64_t per_fixed = D.blocks_per;              // (a multi-device call fixes the partition; cleared here)
     D.blocks_per = 0;
+    const uint64_t *range_off = D.blocks_off, *range_len = D.blocks_len;       // (nlzm_hip_compress_ranges*: the blocks are the caller's ranges of the n bytes; cleared here)
+    D.blocks_off = D.blocks_len = nullptr;
+    if (range_len) {        // the set's shared decisions are those of the equal split of nblocks x its longest range
+        per_fixed = 0;
+        for (uint32_t i = 0; i < nblocks && i < 64; i++) if (range_len[i] > per_fixed) per_fixed = range_len[i];
+    }
     if (!C.inited) return fail(NLZM_HIP_E_NODEVICE, "nlzm_hip_init() has not succeeded");
     if (!nblocks || nblocks > 64) return fail(NLZM_HIP_E_ARG, "nblocks out of range");
     blocks_close(D);
@@ -150,7 +156,7 @@ int nlzm_hip_blocks_begin(const void *d_src, uint64_t n, uint32_t nblocks, uint3
         free_b += D.blocks_pool_size;               // (the allocation kept from the set before is this set's to use)
         const double per_stream = 0.85 * (double)free_b / nblocks;
         Geom g0;
-        make_geom(per_fixed ? per_fixed : container::per_block(n, nblocks), hist_bits_req, g0);
+        make_geom(per_fixed || range_len ? per_fixed : container::per_block(n, nblocks), hist_bits_req, g0);
         const double fixed = 8.0 * ((double)g0.wmask + 1) * 2 + 5e7;     // BT4 tree (widened), the rest
         double left = per_stream - fixed;
         if (left < 2e8) return fail(NLZM_HIP_E_NOMEM, "%u streams of %llu bytes at -window:%u do not fit %.1f GB of free memory", nblocks,
@@ -165,7 +171,8 @@ int nlzm_hip_blocks_begin(const void *d_src, uint64_t n, uint32_t nblocks, uint3
     const uint64_t per = per_fixed ? per_fixed : container::per_block(n, nblocks);     // block i = [i*per, min(n, (i+1)*per))
     D.jobs.resize(nblocks);
     for (uint32_t i = 0; i < nblocks; i++) {
-        container::block_range(n, per, i, D.jobs[i].lo, D.jobs[i].n);
+        if (range_len) { D.jobs[i].lo = range_off[i]; D.jobs[i].n = range_len[i]; }       // (checked against n by the plan: nlzm_container_plan.h)
+        else container::block_range(n, per, i, D.jobs[i].lo, D.jobs[i].n);
         D.jobs[i].bound = nlzm_hip_compress_bound(D.jobs[i].n);
     }
     const auto stream_options = [&](uint32_t i) { return block_stream_options(O, wb, batch, tbits_max, i); };
@@ -492,6 +499,86 @@ int nlzm_hip_compress_blocks_dev(const void *d_src, uint64_t n, uint32_t nblocks
     const uint32_t set_blocks = (uint32_t)(D.opt.container_set_blocks < (int64_t)cap ? D.opt.container_set_blocks : (int64_t)cap);
     if (const int rc = container::make_plan(P, n, nblocks, set_blocks, cap, nlzm_hip_compress_bound, ErrText{ text, sizeof text })) return fail(rc, "%s", text);
     return compress_container(D, P, d_src, hist_bits_req, d_dst, dst_cap, block_len, dst_len);
+}
+
+// The sets of a call on ranges (nlzm_container_plan.h, make_ranges_plan), one after another through compress_block_set with the set's ranges as its
+// blocks: every set reads the caller's whole buffer and writes its streams straight behind those of the set before it.  The one allocation is shared
+// as compress_container shares it; a set that fails has closed itself.
+static int compress_range_sets(DevState &D, const container::RangesPlan &P, const void *d_src, uint64_t n, const uint64_t *off, const uint64_t *len,
+                               uint32_t hist_bits_req, void *d_dst, uint64_t dst_cap, uint64_t *block_len, uint64_t *dst_len)
+{
+    nlzm_hip_stats total{};
+    uint64_t pos = 0, redo = 0;
+    const int64_t keep_pool = D.opt.keep_pool;
+    if (P.sets.size() > 1) D.opt.keep_pool = 1;
+    struct Restore { DevState &D; int64_t keep; ~Restore() { D.opt.keep_pool = keep; if (!keep && D.jobs.empty()) blocks_close(D, true); } } restore{ D, keep_pool };
+    for (const container::RangeSet &S : P.sets) {
+        uint64_t out = 0;
+        D.blocks_off = off + S.first; D.blocks_len = len + S.first;     // (read and cleared by nlzm_hip_blocks_begin)
+        const int rc = compress_block_set(d_src, n, S.count, hist_bits_req, (uint8_t *)d_dst + pos, dst_cap - pos, block_len ? block_len + S.first : nullptr, &out);
+        D.blocks_off = D.blocks_len = nullptr;
+        if (rc) return rc;
+        pos += out;
+        redo += D.redo_streams;
+        D.container_sets++;
+        add_stats(total, D.ctx.stats);
+    }
+    D.ctx.stats = total;
+    D.redo_streams = redo;
+    *dst_len = pos;
+    return 0;
+}
+
+uint64_t nlzm_hip_compress_ranges_bound(uint32_t k, const uint64_t *len)
+{
+    uint64_t sum = 0;
+    return container::ranges_bound(k, len, nlzm_hip_compress_bound, sum) ? sum : 0;
+}
+
+// what both forms check before anything is allocated: the plan of the call (with the device's capacity where there is a device, else with one
+// that only serves the checks), so that a bad argument is NLZM_HIP_E_ARG with or without a device
+static int ranges_plan(DevState &D, container::RangesPlan &P, uint64_t n, uint32_t k, const uint64_t *off, const uint64_t *len)
+{
+    const uint32_t cap = blocks_capacity(D);
+    const uint32_t set_blocks = cap ? (uint32_t)(D.opt.container_set_blocks < (int64_t)cap ? D.opt.container_set_blocks : (int64_t)cap) : 1;
+    char text[512] = "";
+    if (const int rc = container::make_ranges_plan(P, n, k, off, len, set_blocks, cap ? cap : 1, nlzm_hip_compress_bound, ErrText{ text, sizeof text })) return fail(rc, "%s", text);
+    return 0;
+}
+
+int nlzm_hip_compress_ranges_dev(const void *d_src, uint64_t n, uint32_t k, const uint64_t *off, const uint64_t *len, uint32_t hist_bits_req, void *d_dst,
+                                 uint64_t dst_cap, uint64_t *block_len, uint64_t *dst_len)
+{
+    DevState &D = cur();
+    D.container_sets = 0;
+    if (!d_dst || !dst_len || (!d_src && n)) return fail(NLZM_HIP_E_ARG, "null argument");
+    container::RangesPlan P;
+    if (const int rc = ranges_plan(D, P, n, k, off, len)) return rc;
+    if (!D.ctx.inited) return fail(NLZM_HIP_E_NODEVICE, "nlzm_hip_init() has not succeeded");
+    if (dst_cap < P.out_bound) return fail(NLZM_HIP_E_CAPACITY, "dst_cap %llu, the ranges' streams may take %llu (nlzm_hip_compress_ranges_bound)", (unsigned long long)dst_cap, (unsigned long long)P.out_bound);
+    return compress_range_sets(D, P, d_src, n, off, len, hist_bits_req, d_dst, dst_cap, block_len, dst_len);
+}
+
+int nlzm_hip_compress_ranges(const uint8_t *src, uint64_t n, uint32_t k, const uint64_t *off, const uint64_t *len, uint32_t hist_bits_req, uint8_t *dst,
+                             uint64_t dst_cap, uint64_t *block_len, uint64_t *dst_len)
+{
+    DevState &D = cur();
+    if ((!src && n) || !dst || !dst_len) return fail(NLZM_HIP_E_ARG, "null argument");
+    container::RangesPlan P;
+    if (const int rc = ranges_plan(D, P, n, k, off, len)) return rc;
+    if (!D.ctx.inited) return fail(NLZM_HIP_E_NODEVICE, "nlzm_hip_init() has not succeeded");
+    if (dst_cap < P.out_bound) return fail(NLZM_HIP_E_CAPACITY, "dst_cap %llu, the ranges' streams may take %llu (nlzm_hip_compress_ranges_bound)", (unsigned long long)dst_cap, (unsigned long long)P.out_bound);
+    DevBuf in, out;                                 // (neither size is 0: 512 bytes behind the input, a bound of a stream's margin at least)
+    if (const int rc = in.alloc(n + 512)) return rc;
+    if (hipMalloc(&out.p, P.out_bound) != hipSuccess) return fail(NLZM_HIP_E_NOMEM, "output buffer");
+    uint8_t *d_in = in.as<uint8_t>(), *d_out = out.as<uint8_t>();
+    if (hipMemset(d_in + n, 0, 512) != hipSuccess || (n && hipMemcpy(d_in, src, n, hipMemcpyHostToDevice) != hipSuccess))
+        return fail(NLZM_HIP_E_NODEVICE, "copying the input to the device failed");
+    uint64_t got = 0;
+    int rc = nlzm_hip_compress_ranges_dev(d_in, n, k, off, len, hist_bits_req, d_out, P.out_bound, block_len, &got);
+    if (!rc && got && hipMemcpy(dst, d_out, got, hipMemcpyDeviceToHost) != hipSuccess) rc = fail(NLZM_HIP_E_NODEVICE, "copy back failed");
+    if (!rc) *dst_len = got;
+    return rc;
 }
 
 int nlzm_hip_compress_blocks(const uint8_t *src, uint64_t n, uint32_t nblocks, uint32_t hist_bits_req, uint8_t *dst,

@@ -236,6 +236,7 @@ struct DevState {
     uint32_t blocks_hist = 0;
     int64_t blocks_wb = 0;
     uint64_t blocks_per = 0;                        // bytes per block when the caller fixes the partition (0: ceil(n / nblocks))
+    const uint64_t *blocks_off = nullptr, *blocks_len = nullptr;   // the next set's blocks as ranges of the caller's choosing, one entry per block (nlzm_hip_compress_ranges*; read and cleared by nlzm_hip_blocks_begin)
     uint64_t redo_streams = 0;                      // streams of the last block set that were made again as single streams (their pair-list arena had run out)
     uint64_t container_sets = 0;                    // block sets the last nlzm_hip_compress_blocks* call ran one after another (1: the blocks fitted one launch)
     // the rounds of the block set (blocks_step_impl): two are open at a time, and one may stay queued when a step returns
