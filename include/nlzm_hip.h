@@ -234,6 +234,35 @@ int nlzm_hip_cut_points_dev(const void *d_src, uint64_t n, uint32_t avg_bits, ui
 int nlzm_hip_cut_points(const uint8_t *src, uint64_t n, uint32_t avg_bits, uint64_t min_len, uint64_t max_len,
                         uint64_t *cut, uint32_t cut_cap, uint32_t *ncuts);         /* uploads first */
 
+/* ---- equal ranges ------------------------------------------------------------------------------------------------ */
+/* Which of k ranges of ONE buffer hold the same bytes: first_of[i] = the smallest j <= i whose range [off[j], off[j] + len[j]) of the buf_len bytes at
+ * d_buf holds the bytes of range i (a range is equal to itself, so first_of[i] == i says "not seen before").  k: 1 .. 65536; off / len / first_of /
+ * fingerprint: host arrays of k entries.  Ranges may be empty, overlap, repeat and come in any order.  The answer is EXACT: a 64-bit fingerprint of
+ * every range groups them, and every member of a group is compared byte by byte with its representative before it is called equal; a fingerprint
+ * collision costs a second round of compares, never a wrong or a missed duplicate.  Two ranges with the same (off, len) are equal without a compare,
+ * all empty ranges are equal to the first empty one.  A range with len > buf_len - off is NLZM_HIP_E_ARG (the text names it): checked before any
+ * launch, with or without a device.  Reads stay inside the ranges: no padding, no alignment is asked for.
+ * The fingerprint (nlzm_amd/csrc/nlzm_dedup.h; tests/dedup_model.py restates it) is a function of the range's bytes and its length alone: the range
+ * is cut into segments of nlzm_hip_get_counter("dedup_segment_bytes") bytes from its own first byte; a segment's bytes, zeros behind them up to a
+ * multiple of 16, are little-endian 32-bit words w[j]; with K(j) = mix32(j + 1), h = the sum over the 16-byte units u of (w[4u] + K(4u)) * (w[4u + 1]
+ * + K(4u + 1)) + (w[4u + 2] + K(4u + 2)) * (w[4u + 3] + K(4u + 3)), the factors modulo 2^32, the sum modulo 2^64; F = splitmix64((sum over the
+ * segments g of splitmix64(h(g) + (g + 1) * 0x9E3779B97F4A7C15) modulo 2^64) XOR splitmix64(len)).  fingerprint (may be NULL) receives F of every range.
+ * On the device: one wave per segment in ONE launch for all ranges (unaligned 16-byte loads, the tail byte by byte), one wave per range to combine;
+ * per round of compares one wave per 32 KiB chunk of a pair, then one per pair; no atomics.  Only fingerprints and verdicts come back to the host.
+ * Counters of the last call: "dedup_distinct" (ranges that are their own first), "dedup_dup_bytes" (bytes of the ranges that are another's copy),
+ * "dedup_rounds", "dedup_pairs", "dedup_compared_bytes" (the compared pairs' lengths), "dedup_us" (device time of all its launches),
+ * "dedup_segment_bytes" (needs no device); "dedup_ranges" reads the option of that name as it stands.
+ * With option "dedup_ranges" set, nlzm_hip_compress_ranges* finds first_of first and compresses the distinct ranges only -- stream i is a function of
+ * range i's bytes and hist_bits_req alone, so equal ranges have equal streams: the distinct ranges, in order of first occurrence, run as sets into a
+ * scratch allocation of the library's sized by their bound (NLZM_HIP_E_NOMEM when there is no room), and one launch of the range reader's gather kernel
+ * puts stream first_of[i] at stream i's place ("dedup_gather_us").  d_dst, block_len and *dst_len are byte for byte what the call gives with the option
+ * off, dst_cap is held to the same bound; "container_sets" counts the sets that ran and nlzm_hip_get_stats sums over the streams that were compressed.
+ * With every range distinct the call runs what it runs with the option off. */
+int nlzm_hip_equal_ranges_dev(const void *d_buf, uint64_t buf_len, uint32_t k, const uint64_t *off, const uint64_t *len,
+                              uint32_t *first_of, uint64_t *fingerprint /* may be NULL */);
+int nlzm_hip_equal_ranges(const uint8_t *buf, uint64_t buf_len, uint32_t k, const uint64_t *off, const uint64_t *len,
+                          uint32_t *first_of, uint64_t *fingerprint /* may be NULL */);      /* uploads first */
+
 /* ---- streaming host input and output ---------------------- */
 /* The reference reads its input and writes its frames as it goes (NLZM.cpp:1774-1778, :1853, :1870-1885).  Here the
  * caller announces the input's length, hands the bytes over in pieces, in order (any piece size; a piece travels through
@@ -423,7 +452,10 @@ int nlzm_hip_read_ranges(const uint8_t *src, uint64_t src_len, uint32_t nblocks,
  * "stage_report" (1: the stages' cycle accounting of
  * every finished stream, and of a block set per stream, on stderr; a container compressed in sets reports set by set);
  * "container_set_blocks" (default 32, 1 .. the device's capacity -- 64 on an MI355X: blocks per set of a container that nlzm_hip_compress_blocks* compresses
- * in sets); "decode_ring" (0, 65536 or 16384: which one-shot decode kernel runs, see the decoding section; read by every decode launch).
+ * in sets); "decode_ring" (0, 65536 or 16384: which one-shot decode kernel runs, see the decoding section; read by every decode launch);
+ * "dedup_ranges" (default 0; 1: nlzm_hip_compress_ranges* does not compress a range again whose bytes an earlier range of the call holds, see the
+ * equal-ranges section; read by every such call, the process's rather than a device's); test only: "test_dedup_hash_bits" (default 64, 0 .. 64: the
+ * equal-range finder keeps that many low bits of every fingerprint before it groups, so that its rounds can be exercised).
  * There are no environment knobs.
  * None of them changes a byte of the output.  The options are read when a stream or a block set is opened
  * (nlzm_hip_stream_begin, nlzm_hip_blocks_begin, nlzm_hip_feed_begin, the one-call entries): what is open keeps what it was opened with.

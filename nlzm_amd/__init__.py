@@ -38,6 +38,7 @@ ABI_SYMBOLS = [
     "nlzm_hip_decode_begin_dev", "nlzm_hip_decode_begin", "nlzm_hip_decode_step", "nlzm_hip_decode_extend_dev", "nlzm_hip_decode_fetch",
     "nlzm_hip_decode_finish", "nlzm_hip_decode_abandon",
     "nlzm_hip_compress_ranges_dev", "nlzm_hip_compress_ranges", "nlzm_hip_compress_ranges_bound", "nlzm_hip_cut_points_dev", "nlzm_hip_cut_points",
+    "nlzm_hip_equal_ranges_dev", "nlzm_hip_equal_ranges",
 ]
 DECODE_MORE = 1          # NLZM_HIP_DECODE_MORE
 TO_THE_END = (1 << 64) - 1
@@ -157,6 +158,9 @@ def load_library() -> C.CDLL:
         lib.nlzm_hip_compress_ranges_bound.restype = C.c_uint64
         lib.nlzm_hip_cut_points_dev.argtypes = [C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint64, C.c_uint64, u64p, C.c_uint32, u32p]
         lib.nlzm_hip_cut_points.argtypes = [C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint64, C.c_uint64, u64p, C.c_uint32, u32p]
+    if hasattr(lib, "nlzm_hip_equal_ranges"):      # (absent from older diagnostic builds loaded through NLZM_LIB)
+        lib.nlzm_hip_equal_ranges_dev.argtypes = [C.c_void_p, C.c_uint64, C.c_uint32, u64p, u64p, u32p, u64p]
+        lib.nlzm_hip_equal_ranges.argtypes = [C.c_void_p, C.c_uint64, C.c_uint32, u64p, u64p, u32p, u64p]
     _lib = lib
     return lib
 
@@ -219,10 +223,35 @@ def compress_blocks(data, nblocks: int, hist_bits: int = 22) -> list[bytes]:
     return out
 
 
-def compress_ranges(data, ranges, hist_bits: int = 22) -> list[bytes]:
+def equal_ranges(data, ranges, fingerprints=None) -> list[int]:
+    """first_of for the (offset, length) ranges of `data`, found on the device (nlzm_hip_equal_ranges): first_of[i] is the smallest j <= i whose
+    range holds the same bytes as range i.  Exact: fingerprints group the ranges, byte compares decide.  fingerprints: a list that receives every
+    range's 64-bit fingerprint (the rule: tests/dedup_model.py)."""
+    lib = load_library()
+    src = _bytes_in(data)
+    n, k = int(src.size), len(ranges)
+    if not 1 <= k <= 65536:
+        raise ValueError("ranges: 1 to 65536")
+    off, ln = (C.c_uint64 * k)(*[int(o) for o, _ in ranges]), (C.c_uint64 * k)(*[int(l) for _, l in ranges])
+    first, fp = (C.c_uint32 * k)(), (C.c_uint64 * k)()
+    _chk(lib.nlzm_hip_equal_ranges(src.ctypes.data if n else None, n, k, off, ln, first, fp))
+    if fingerprints is not None:
+        fingerprints[:] = [int(x) for x in fp]
+    return [int(x) for x in first]
+
+
+def compress_ranges(data, ranges, hist_bits: int = 22, dedup: bool = False) -> list[bytes]:
     """One stream per (offset, length) range of `data`, all in one call: the ranges may be empty, overlap, repeat and come in any order; stream i
     is the reference's encode_file (NLZM.cpp:1711) run on data[off:off + length].  Up to a launch's capacity (64 on an MI355X) they are one block
-    set, more of them run in sets of consecutive ranges (counter "container_sets")."""
+    set, more of them run in sets of consecutive ranges (counter "container_sets").  dedup: option "dedup_ranges" for this call -- a range whose
+    bytes an earlier one holds is not compressed again, its stream is a copy (the same bytes come back; the "dedup_*" counters say what was saved)."""
+    if dedup:
+        was = counter("dedup_ranges")        # (the option as it stands)
+        set_option("dedup_ranges", 1)
+        try:
+            return compress_ranges(data, ranges, hist_bits)
+        finally:
+            set_option("dedup_ranges", was)
     lib = load_library()
     src = _bytes_in(data)
     n, k = int(src.size), len(ranges)

@@ -265,6 +265,7 @@ int main(int argc, char **argv)
     bool with_crc = false;                          // -crc (not in the reference): c keeps every block's CRC32, hashed on the device, in the index (NLZMIDX 2); d / t check them
     bool on_gpu = false;                            // -gpu (not in the reference): d / t decode on the device; without it they are host-only and need none
     uint32_t cdc_bits = 0;                          // -cdc:B (not in the reference): c cuts the blocks by content on the device, 2^B bytes a block on average
+    bool dedup = false;                             // -dedup (not in the reference): with -cdc:B, c does not compress a block again whose bytes an earlier block holds
     uint32_t steps_k = 0;                           // -steps:K (not in the reference): d -gpu / t -gpu decode in steps of K frames per block
     std::vector<ByteRange> ranges;                  // -range:off:len (not in the reference): what x writes, in this order
     while (argc >= 2 && *argv[1] == '-') {
@@ -292,6 +293,8 @@ int main(int argc, char **argv)
             for (; ok && *p >= '0' && *p <= '9'; p++) { v = v * 10 + (unsigned)(*p - '0'); if (v > 30) ok = false; }
             if (!ok || *p || v < 10) { printf("Error: -cdc:B takes B from 10 to 30 (blocks of 2^B bytes on average)\n"); return -1; }
             cdc_bits = v;
+        } else if (!strcmp(arg, "dedup")) {
+            dedup = true;
         } else if (!strcmp(arg, "verify")) {
             verify = true;
         } else if (!strcmp(arg, "crc")) {
@@ -327,6 +330,7 @@ int main(int argc, char **argv)
     }
     const int cmd = argc >= 2 ? (argv[1][0] | 0x20) : 0;
     if (cdc_bits && (nblocks > 1 || ngpus)) { printf("Error: -cdc:B cuts the blocks by content; it does not go together with -blocks:k or -gpus:g\n"); return -1; }
+    if (dedup && !cdc_bits) { printf("Error: -dedup skips the duplicates among the blocks that -cdc:B cuts; it needs -cdc:B\n"); return -1; }
     if (ngpus && nblocks > 64) { nblocks = 64; printf("Blocks: %d (on each GPU: a launch holds no more)\n", nblocks); }
     if (steps_k && !(on_gpu && ((argc == 4 && cmd == 'd') || (argc == 3 && cmd == 't')))) { printf("Error: -steps:K is for d -gpu and t -gpu\n"); return -1; }
     if (argc == 4 && cmd == 'c') {
@@ -441,6 +445,7 @@ int main(int argc, char **argv)
         std::vector<uint64_t> blen(nstreams);
         std::vector<int> devs;
         for (uint32_t d = 0; d < ngpus; d++) devs.push_back((int)d);
+        if (dedup && nlzm_hip_set_option("dedup_ranges", 1)) { printf("Error: %s\n", nlzm_hip_last_error()); fclose(fout); remove(argv[3]); return -1; }
         const int rc = cdc_bits ? nlzm_hip_compress_ranges(in.data(), in.size(), nstreams, boff.data(), braw.data(), hist_bits, out.data(), out.size(), blen.data(), &out_n)
                      : ngpus ? nlzm_hip_compress_blocks_multi(devs.data(), ngpus, nblocks, in.data(), in.size(), hist_bits, out.data(), out.size(), blen.data(), &out_n)
                      : nblocks > 1 ? nlzm_hip_compress_blocks(in.data(), in.size(), nblocks, hist_bits, out.data(), out.size(), blen.data(), &out_n)
@@ -449,6 +454,12 @@ int main(int argc, char **argv)
         (void)t0;
         if (rc) { printf("Error: %s\n", nlzm_hip_last_error()); fclose(fout); remove(argv[3]); return -1; }
         if (nstreams == 1) blen[0] = out_n;
+        if (dedup) {        // (the finder's counters of the call: the blocks that were another's copy, and their bytes)
+            uint64_t distinct = nstreams, dup_bytes = 0;
+            (void)nlzm_hip_get_counter("dedup_distinct", &distinct);
+            (void)nlzm_hip_get_counter("dedup_dup_bytes", &dup_bytes);
+            printf("Duplicates: %" PRIu64 " of %u blocks (%" PRIu64 " bytes) not compressed again\n", (uint64_t)nstreams - distinct, nstreams, dup_bytes);
+        }
         if (verify) {
             // the stream(s) decoded on the device, one workgroup each, and compared there with the input; neither comes back to the host
             uint64_t first = 0, decoded = 0;
@@ -761,6 +772,7 @@ int main(int argc, char **argv)
                "\t-blocks:k = (this build) compress k independent blocks, 1 to 65536: as many at once as a launch holds (64), more of them\n"
                "\t            in sets one after another; d/t read the streams back to back\n"
                "\t-cdc:B = (this build) c cuts the blocks by content on the GPU, 2^B bytes on average (B 10 to 30): an edit changes the blocks around it only\n"
+               "\t-dedup = (this build) with -cdc:B: a block whose bytes an earlier block holds is not compressed again, its stream is a copy (the same container)\n"
                "\t-gpus:g = (this build) the blocks on GPUs 0..g-1 of this node, -blocks:k of them on each (64 at most)\n"
                "\t-verify = (this build) c decodes what it wrote on the GPU, one workgroup per stream, compares it with the input\n"
                "\t          and removes the output if they differ\n"

@@ -20,6 +20,7 @@
 
 #include "nlzm_host_state.h"
 #include "nlzm_cut_host.h"
+#include "nlzm_dedup_host.h"
 #include "nlzm_report.h"
 #include "nlzm_stream_plan.h"
 
@@ -803,6 +804,7 @@ int nlzm_hip_get_counter(const char *key, uint64_t *value)
     if (!strncmp(key, "crc_", 4)) return nlzm::crc_counter(key, value);
     if (!strncmp(key, "range_", 6)) return nlzm::range_counter(key, value);
     if (!strncmp(key, "cut_", 4)) return nlzm::cut_counter(key, value);
+    if (!strncmp(key, "dedup_", 6)) return nlzm::dedup_counter(key, value);
     if (C.open) { const int rc = refresh_stats(C, D.opt.report != 0); if (rc) return rc; }
     if (compress_counter(key, C.prof_last, C.wc_last, C.stats.positions, value)) return 0;
     if (!strcmp(key, "block_pool_bytes")) { *value = D.blocks_pool_size; return 0; }
@@ -866,6 +868,7 @@ int nlzm_hip_set_option(const char *key, int64_t value)
         if (value != 1) return fail(NLZM_HIP_E_ARG, "workers: only 1 is supported");
         return 0;
     }
+    if (const int rc = nlzm::dedup_set_option(key, value); rc <= 0) return rc;     // ("dedup_ranges", "test_dedup_hash_bits": nlzm_hip_dedup.cpp keeps them)
     for (const auto &o : kOptions) {
         if (strcmp(key, o.key)) continue;
         const bool ranged = o.kind == kOptRange || o.kind == kOptLanes;

@@ -12,6 +12,7 @@
 
 #include "nlzm_host_state.h"
 #include "nlzm_container_plan.h"
+#include "nlzm_dedup_host.h"
 #include "nlzm_launch.h"
 #include "nlzm_report.h"
 
@@ -546,6 +547,44 @@ static int ranges_plan(DevState &D, container::RangesPlan &P, uint64_t n, uint32
     return 0;
 }
 
+// Option "dedup_ranges": the ranges whose bytes an earlier range of the call holds are not compressed again (stream i is a function of range i's bytes and
+// hist_bits_req alone: equal bytes, equal streams).  first_of from the device (nlzm_hip_dedup.cpp); the distinct ranges, in order of first occurrence,
+// through the same plan and sets into a scratch allocation sized by their bound; ONE gather launch puts stream first_of[i] at stream i's place.
+// *done = 0: every range is distinct, and the caller runs what it runs without the option.
+static int compress_ranges_dedup(DevState &D, const void *d_src, uint64_t n, uint32_t k, const uint64_t *off, const uint64_t *len, uint32_t hist_bits_req, void *d_dst,
+                                 uint64_t *block_len, uint64_t *dst_len, bool *done)
+{
+    *done = false;
+    std::vector<uint32_t> first_of(k), slot(k, 0);
+    if (const int rc = dedup_first_of(d_src, n, k, off, len, first_of.data())) return rc;
+    std::vector<uint64_t> doff, dlen;
+    for (uint32_t i = 0; i < k; i++) if (first_of[i] == i) { slot[i] = (uint32_t)doff.size(); doff.push_back(off[i]); dlen.push_back(len[i]); }
+    const uint32_t kd = (uint32_t)doff.size();
+    if (kd == k) return 0;
+    container::RangesPlan P;
+    if (const int rc = ranges_plan(D, P, n, kd, doff.data(), dlen.data())) return rc;
+    DevBuf scratch;
+    if (hipMalloc(&scratch.p, P.out_bound) != hipSuccess) {
+        (void)hipGetLastError(); scratch.p = nullptr;
+        return fail(NLZM_HIP_E_NOMEM, "no %llu bytes of device memory for the streams of the %u distinct ranges", (unsigned long long)P.out_bound, kd);
+    }
+    std::vector<uint64_t> dblen(kd), dpos(kd), from(k), to(k), blen(k);
+    uint64_t got = 0, pos = 0;
+    if (const int rc = compress_range_sets(D, P, d_src, n, doff.data(), dlen.data(), hist_bits_req, scratch.p, P.out_bound, dblen.data(), &got)) return rc;
+    for (uint32_t j = 0; j < kd; j++) { dpos[j] = pos; pos += dblen[j]; }
+    pos = 0;
+    for (uint32_t i = 0; i < k; i++) {
+        const uint32_t j = slot[first_of[i]];
+        from[i] = dpos[j]; to[i] = pos; blen[i] = dblen[j];
+        pos += blen[i];
+    }
+    if (const int rc = dedup_place(scratch.as<uint8_t>(), (uint8_t *)d_dst, k, from.data(), to.data(), blen.data())) return rc;
+    if (block_len) memcpy(block_len, blen.data(), (size_t)k * sizeof(uint64_t));
+    *dst_len = pos;
+    *done = true;
+    return 0;
+}
+
 int nlzm_hip_compress_ranges_dev(const void *d_src, uint64_t n, uint32_t k, const uint64_t *off, const uint64_t *len, uint32_t hist_bits_req, void *d_dst,
                                  uint64_t dst_cap, uint64_t *block_len, uint64_t *dst_len)
 {
@@ -556,6 +595,11 @@ int nlzm_hip_compress_ranges_dev(const void *d_src, uint64_t n, uint32_t k, cons
     if (const int rc = ranges_plan(D, P, n, k, off, len)) return rc;
     if (!D.ctx.inited) return fail(NLZM_HIP_E_NODEVICE, "nlzm_hip_init() has not succeeded");
     if (dst_cap < P.out_bound) return fail(NLZM_HIP_E_CAPACITY, "dst_cap %llu, the ranges' streams may take %llu (nlzm_hip_compress_ranges_bound)", (unsigned long long)dst_cap, (unsigned long long)P.out_bound);
+    if (dedup_ranges_option()) {
+        bool done = false;
+        const int rc = compress_ranges_dedup(D, d_src, n, k, off, len, hist_bits_req, d_dst, block_len, dst_len, &done);
+        if (rc || done) return rc;
+    }
     return compress_range_sets(D, P, d_src, n, off, len, hist_bits_req, d_dst, dst_cap, block_len, dst_len);
 }
 
