@@ -263,6 +263,43 @@ int nlzm_hip_equal_ranges_dev(const void *d_buf, uint64_t buf_len, uint32_t k, c
 int nlzm_hip_equal_ranges(const uint8_t *buf, uint64_t buf_len, uint32_t k, const uint64_t *off, const uint64_t *len,
                           uint32_t *first_of, uint64_t *fingerprint /* may be NULL */);      /* uploads first */
 
+/* ---- typed ranges: byte planes ----------------------------------------------------------------------------------------- */
+/* The filter in front of the coder for arrays of fixed-size elements (bf16 / fp16 / fp32 weights, int32 / int64 ids, offsets): every element's byte j
+ * goes to plane j, so that the bytes that carry structure -- sign and exponent, the high bytes of small integers -- lie together.  The rule
+ * (nlzm_amd/csrc/nlzm_planes.h; tests/planes_model.py restates it): for a range x of n bytes and an element size e in {1, 2, 4, 8}, m = n div e,
+ * planes_e(x) = y with y[j m + i] = x[i e + j] for 0 <= j < e, 0 <= i < m, and y[e m + t] = x[e m + t] for the n - e m tail bytes.  e = 1 is the
+ * identity; both directions keep the length; elements are counted from the range's own first byte, no address and no alignment enters.
+ * nlzm_hip_planes*: k ranges in ONE launch (k: 1 .. 65536; src_off / dst_off / len / elem: host arrays of k entries): range i is len[i] bytes at
+ * src_off[i] of the src_len bytes at d_src and goes to dst_off[i] of the dst_len bytes at d_dst, filtered (inverse == 0) or with the filter undone
+ * (inverse != 0).  Source ranges may be empty, overlap and repeat.  All NLZM_HIP_E_ARG, the text naming the range, checked before any launch, with or
+ * without a device: destinations that overlap each other, the two buffers overlapping (there is no in-place form), an elem outside {1, 2, 4, 8}, a
+ * range that runs over its buffer.  Reads stay inside the source ranges and writes inside the destination ranges: no padding, no alignment is asked
+ * for, of either side or of one relative to the other.  The host form uploads the source and copies back the destination ranges only: the bytes
+ * between them stay the caller's.
+ * On the device: one wave per segment of nlzm_hip_get_counter("planes_segment_bytes") bytes of a range keeps an image of the segment's planes in LDS;
+ * every byte is loaded once and stored once, in 16-byte units but for up to 15 bytes at the ends of a run; no atomics.
+ * nlzm_hip_compress_ranges_typed*: nlzm_hip_compress_ranges* with an element size per range.  The ranges are filtered in one launch into a scratch
+ * allocation of the library's (the sum of len and the 128 bytes behind it; NLZM_HIP_E_NOMEM when there is no room, and nothing is left open), and
+ * nlzm_hip_compress_ranges_dev runs on that scratch: stream i is byte for byte the reference run on planes_elem[i](range i), the reference
+ * decompressor reads it, and option "dedup_ranges" is honoured as it stands (on the filtered bytes).  Nothing but the reads of d_src differs:
+ * arguments, errors, bound and counters are the untyped call's.  elem == NULL, or every elem 1, IS the untyped call, with no scratch.
+ * nlzm_hip_decompress_blocks_typed*: nlzm_hip_decompress_blocks* with an element size per block: block_len / raw_len / d_dst == NULL (a size pass,
+ * which needs no filter) as there; the blocks are decoded into scratch (sized first when raw_len is NULL) and one inverse launch puts every block at
+ * its place in d_dst.  elem == NULL, or every elem 1, is the untyped call.
+ * Counters of the last call: "planes_us" (device time of its planes launch), "planes_bytes" (what it moved), "planes_segment_bytes" (needs no device). */
+int nlzm_hip_planes_dev(const void *d_src, uint64_t src_len, void *d_dst, uint64_t dst_len, uint32_t k,
+                        const uint64_t *src_off, const uint64_t *dst_off, const uint64_t *len, const uint8_t *elem, int inverse);
+int nlzm_hip_planes(const uint8_t *src, uint64_t src_len, uint8_t *dst, uint64_t dst_len, uint32_t k,
+                    const uint64_t *src_off, const uint64_t *dst_off, const uint64_t *len, const uint8_t *elem, int inverse);      /* uploads, downloads */
+int nlzm_hip_compress_ranges_typed_dev(const void *d_src, uint64_t n, uint32_t k, const uint64_t *off, const uint64_t *len, const uint8_t *elem,
+                                       uint32_t hist_bits_req, void *d_dst, uint64_t dst_cap, uint64_t *block_len, uint64_t *dst_len);
+int nlzm_hip_compress_ranges_typed(const uint8_t *src, uint64_t n, uint32_t k, const uint64_t *off, const uint64_t *len, const uint8_t *elem,
+                                   uint32_t hist_bits_req, uint8_t *dst, uint64_t dst_cap, uint64_t *block_len, uint64_t *dst_len);
+int nlzm_hip_decompress_blocks_typed_dev(const void *d_src, uint64_t src_len, uint32_t nblocks, const uint64_t *block_len, const uint64_t *raw_len,
+                                         const uint8_t *elem, void *d_dst, uint64_t dst_cap, uint64_t *raw_len_out, uint64_t *dst_len);
+int nlzm_hip_decompress_blocks_typed(const uint8_t *src, uint64_t src_len, uint32_t nblocks, const uint64_t *block_len, const uint64_t *raw_len,
+                                     const uint8_t *elem, uint8_t *dst, uint64_t dst_cap, uint64_t *raw_len_out, uint64_t *dst_len);
+
 /* ---- streaming host input and output ---------------------- */
 /* The reference reads its input and writes its frames as it goes (NLZM.cpp:1774-1778, :1853, :1870-1885).  Here the
  * caller announces the input's length, hands the bytes over in pieces, in order (any piece size; a piece travels through

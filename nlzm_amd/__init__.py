@@ -39,6 +39,8 @@ ABI_SYMBOLS = [
     "nlzm_hip_decode_finish", "nlzm_hip_decode_abandon",
     "nlzm_hip_compress_ranges_dev", "nlzm_hip_compress_ranges", "nlzm_hip_compress_ranges_bound", "nlzm_hip_cut_points_dev", "nlzm_hip_cut_points",
     "nlzm_hip_equal_ranges_dev", "nlzm_hip_equal_ranges",
+    "nlzm_hip_planes_dev", "nlzm_hip_planes", "nlzm_hip_compress_ranges_typed_dev", "nlzm_hip_compress_ranges_typed",
+    "nlzm_hip_decompress_blocks_typed_dev", "nlzm_hip_decompress_blocks_typed",
 ]
 DECODE_MORE = 1          # NLZM_HIP_DECODE_MORE
 TO_THE_END = (1 << 64) - 1
@@ -161,6 +163,13 @@ def load_library() -> C.CDLL:
     if hasattr(lib, "nlzm_hip_equal_ranges"):      # (absent from older diagnostic builds loaded through NLZM_LIB)
         lib.nlzm_hip_equal_ranges_dev.argtypes = [C.c_void_p, C.c_uint64, C.c_uint32, u64p, u64p, u32p, u64p]
         lib.nlzm_hip_equal_ranges.argtypes = [C.c_void_p, C.c_uint64, C.c_uint32, u64p, u64p, u32p, u64p]
+    if hasattr(lib, "nlzm_hip_planes"):            # (absent from older diagnostic builds loaded through NLZM_LIB)
+        lib.nlzm_hip_planes_dev.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_uint32, u64p, u64p, u64p, u8p, C.c_int]
+        lib.nlzm_hip_planes.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_uint32, u64p, u64p, u64p, u8p, C.c_int]
+        lib.nlzm_hip_compress_ranges_typed_dev.argtypes = [C.c_void_p, C.c_uint64, C.c_uint32, u64p, u64p, u8p, C.c_uint32, C.c_void_p, C.c_uint64, u64p, u64p]
+        lib.nlzm_hip_compress_ranges_typed.argtypes = [C.c_void_p, C.c_uint64, C.c_uint32, u64p, u64p, u8p, C.c_uint32, C.c_void_p, C.c_uint64, u64p, u64p]
+        lib.nlzm_hip_decompress_blocks_typed_dev.argtypes = [C.c_void_p, C.c_uint64, C.c_uint32, u64p, u64p, u8p, C.c_void_p, C.c_uint64, u64p, u64p]
+        lib.nlzm_hip_decompress_blocks_typed.argtypes = [C.c_void_p, C.c_uint64, C.c_uint32, u64p, u64p, u8p, C.c_void_p, C.c_uint64, u64p, u64p]
     _lib = lib
     return lib
 
@@ -268,6 +277,148 @@ def compress_ranges(data, ranges, hist_bits: int = 22, dedup: bool = False) -> l
         out.append(dst[pos: pos + int(lens[i])].tobytes())
         pos += int(lens[i])
     assert pos == out_len.value
+    return out
+
+
+def _with_dedup(dedup: bool, call):
+    """call() with option "dedup_ranges" set for its duration when dedup is true, the option as it stood afterwards"""
+    if not dedup:
+        return call()
+    was = counter("dedup_ranges")
+    set_option("dedup_ranges", 1)
+    try:
+        return call()
+    finally:
+        set_option("dedup_ranges", was)
+
+
+def planes(data, ranges, elems, inverse: bool = False) -> list[bytes]:
+    """The byte planes of every (offset, length) range of `data` at its element size (1, 2, 4 or 8), made on the device in one launch
+    (nlzm_hip_planes; the rule: tests/planes_model.py): byte j of every element goes to plane j, the tail bytes behind the last whole element stay.
+    inverse: the filter undone.  The ranges may be empty, overlap and repeat; one result per range."""
+    lib = load_library()
+    src = _bytes_in(data)
+    n, k = int(src.size), len(ranges)
+    if not 1 <= k <= 65536 or len(elems) != k:
+        raise ValueError("ranges: 1 to 65536, one element size each")
+    lens = [int(l) for _, l in ranges]
+    ok = all(0 <= l < 1 << 48 for l in lens)       # (a length that cannot be: the library names the range, and nothing is written)
+    at, total = [], 0
+    for l in lens:
+        at.append(total)
+        total += l if ok else 0
+    off, ln, to = (C.c_uint64 * k)(*[int(o) for o, _ in ranges]), (C.c_uint64 * k)(*lens), (C.c_uint64 * k)(*at)
+    el = (C.c_uint8 * k)(*[int(e) if 0 <= int(e) < 256 else 0 for e in elems])
+    dst = np.empty(max(1, total), dtype=np.uint8)
+    _chk(lib.nlzm_hip_planes(src.ctypes.data if n else None, n, dst.ctypes.data, total, k, off, to, ln, el, 1 if inverse else 0))
+    return [dst[a: a + l].tobytes() for a, l in zip(at, lens)]
+
+
+def compress_typed(data, ranges, elems, hist_bits: int = 22, dedup: bool = False) -> list[bytes]:
+    """compress_ranges with an element size (1, 2, 4 or 8) per range: stream i is the reference's encode_file run on the byte planes of range i
+    (nlzm_hip_compress_ranges_typed), which the reference decompressor reads and planes(..., inverse=True) -- one line of numpy -- undoes.
+    elems None: compress_ranges itself."""
+    lib = load_library()
+    src = _bytes_in(data)
+    n, k = int(src.size), len(ranges)
+    if not 1 <= k <= 65536 or (elems is not None and len(elems) != k):
+        raise ValueError("ranges: 1 to 65536, one element size each")
+    off, ln = (C.c_uint64 * k)(*[int(o) for o, _ in ranges]), (C.c_uint64 * k)(*[int(l) for _, l in ranges])
+    el = (C.c_uint8 * k)(*[int(e) if 0 <= int(e) < 256 else 0 for e in elems]) if elems is not None else None
+    cap = int(lib.nlzm_hip_compress_ranges_bound(k, ln))
+    dst = np.empty(max(1, cap), dtype=np.uint8)
+    lens = (C.c_uint64 * k)()
+    out_len = C.c_uint64(0)
+    _with_dedup(dedup, lambda: _chk(lib.nlzm_hip_compress_ranges_typed(src.ctypes.data if n else None, n, k, off, ln, el, hist_bits, dst.ctypes.data, cap, lens,
+                                                                        C.byref(out_len))))
+    out, pos = [], 0
+    for i in range(k):
+        out.append(dst[pos: pos + int(lens[i])].tobytes())
+        pos += int(lens[i])
+    assert pos == out_len.value
+    return out
+
+
+def decompress_typed(blob, block_lens, raw_lens, elems) -> list[bytes]:
+    """The blocks of a typed container (the streams of compress_typed, joined) decoded on the device with the filter undone
+    (nlzm_hip_decompress_blocks_typed): one result per block.  block_lens / raw_lens may be None (the hop over the frame headers; a size pass)."""
+    lib = load_library()
+    src = _bytes_in(blob)
+    k = len(elems)
+    for name, v in (("block_lens", block_lens), ("raw_lens", raw_lens)):
+        if v is not None and len(v) != k:
+            raise ValueError(f"{name}: one entry per block")
+    blen = (C.c_uint64 * k)(*[int(x) for x in block_lens]) if block_lens is not None else None
+    raw = (C.c_uint64 * max(1, k))(*[int(x) for x in raw_lens]) if raw_lens is not None else None
+    el = (C.c_uint8 * max(1, k))(*[int(e) if 0 <= int(e) < 256 else 0 for e in elems])
+    got, total = (C.c_uint64 * max(1, k))(), C.c_uint64(0)
+    if raw is None:
+        _chk(lib.nlzm_hip_decompress_blocks_typed(src.ctypes.data, src.size, k, blen, None, el, None, 0, got, C.byref(total)))
+        raw = got
+    cap = sum(int(raw[i]) for i in range(k))
+    dst = np.empty(max(1, cap), dtype=np.uint8)
+    _chk(lib.nlzm_hip_decompress_blocks_typed(src.ctypes.data, src.size, k, blen, raw, el, dst.ctypes.data, cap, got, C.byref(total)))
+    out, pos = [], 0
+    for i in range(k):
+        out.append(dst[pos: pos + int(got[i])].tobytes())
+        pos += int(got[i])
+    assert pos == total.value
+    return out
+
+
+def _tensor_elem(t) -> int:
+    return t.element_size() if t.element_size() in (2, 4, 8) else 1
+
+
+def compress_tensors(tensors, hist_bits: int = 22, dedup: bool = False):
+    """A list of torch tensors (any device, any dtype) as one block container in device memory, one block per tensor, filtered at the tensor's element
+    size (1 when it is not 2, 4 or 8): the tensors are viewed as bytes and concatenated on the GPU, with the padding the compress path reads behind
+    them, and nlzm_hip_compress_ranges_typed_dev runs on data_ptr().  Returns (container, meta): a device uint8 tensor and a list of
+    (block_len, raw_len, elem, dtype, shape) per tensor -- what decompress_tensors takes."""
+    import torch
+    lib = load_library()
+    k = len(tensors)
+    if not 1 <= k <= 65536:
+        raise ValueError("tensors: 1 to 65536")
+    dev = torch.device("cuda", torch.cuda.current_device())
+    flat = [t.detach().contiguous().reshape(-1).view(torch.uint8).to(dev) for t in tensors]
+    lens = [int(f.numel()) for f in flat]
+    data = torch.cat(flat + [torch.zeros(128, dtype=torch.uint8, device=dev)])
+    at, n = [], 0
+    for l in lens:
+        at.append(n)
+        n += l
+    off, ln = (C.c_uint64 * k)(*at), (C.c_uint64 * k)(*lens)
+    el = (C.c_uint8 * k)(*[_tensor_elem(t) for t in tensors])
+    cap = int(lib.nlzm_hip_compress_ranges_bound(k, ln))
+    out = torch.empty(max(1, cap), dtype=torch.uint8, device=dev)
+    blen, got = (C.c_uint64 * k)(), C.c_uint64(0)
+    torch.cuda.synchronize()
+    _with_dedup(dedup, lambda: _chk(lib.nlzm_hip_compress_ranges_typed_dev(data.data_ptr(), n, k, off, ln, el, hist_bits, out.data_ptr(), cap, blen, C.byref(got))))
+    meta = [(int(blen[i]), lens[i], int(el[i]), tensors[i].dtype, tuple(tensors[i].shape)) for i in range(k)]
+    return out[: got.value].clone(), meta
+
+
+def decompress_tensors(container, meta):
+    """The inverse of compress_tensors: the tensors, on the container's device, bit for bit."""
+    import torch
+    lib = load_library()
+    k = len(meta)
+    if not 1 <= k <= 65536:
+        raise ValueError("meta: 1 to 65536 entries")
+    blen, raw = (C.c_uint64 * k)(*[int(m[0]) for m in meta]), (C.c_uint64 * k)(*[int(m[1]) for m in meta])
+    el = (C.c_uint8 * k)(*[int(m[2]) for m in meta])
+    total = sum(int(m[1]) for m in meta)
+    src = container.contiguous()
+    dst = torch.empty(max(1, total), dtype=torch.uint8, device=src.device)
+    got = C.c_uint64(0)
+    torch.cuda.synchronize()
+    _chk(lib.nlzm_hip_decompress_blocks_typed_dev(src.data_ptr(), int(src.numel()), k, blen, raw, el, dst.data_ptr(), total, None, C.byref(got)))
+    assert got.value == total
+    out, pos = [], 0
+    for _, r, _, dtype, shape in meta:
+        out.append(dst[pos: pos + r].clone().view(dtype).reshape(shape))
+        pos += r
     return out
 
 
@@ -595,6 +746,52 @@ def read_index(path):
     if expect != n_out or raw_sum != n_in:
         raise ValueError(f"{path}: the blocks' lengths sum to {expect} / {raw_sum}, the header says {n_out} / {n_in}")
     return lens, raws, (crcs if ver == 2 else None)
+
+
+def read_index_typed(path):
+    """read_index for every index version: (block_lens, raw_lens, crcs or None, elems).  Version 3 (`nlzm c -elem:E`) holds `off len raw CRC elem` per
+    block, the CRC32s of the RAW bytes; versions 1 and 2 answer through read_index, with every element size 1.  The structural checks are read_index's,
+    and an element size outside 1, 2, 4, 8 is a ValueError."""
+    words = open(path, "r").read().split()
+    if len(words) < 2 or words[0] != "NLZMIDX" or words[1] != "3":
+        lens, raws, crcs = read_index(path)
+        return lens, raws, crcs, [1] * len(lens)
+    M = 1 << 64
+
+    def num(w, base=10):
+        try:
+            v = int(w, base)
+        except ValueError:
+            raise ValueError(f"{path}: {w!r} is not a number") from None
+        if not 0 <= v < M:
+            raise ValueError(f"{path}: {w} does not fit 64 bits")
+        return v
+
+    if len(words) < 6:
+        raise ValueError(f"{path}: not an NLZMIDX 3 file")
+    k, n_in, n_out = num(words[2]), num(words[3]), num(words[4])
+    if not 1 <= k <= 65536 or len(words) != 6 + 5 * k:
+        raise ValueError(f"{path}: {k} blocks do not fit the file's {len(words)} fields")
+    if num(words[5], 16) >= 1 << 32:
+        raise ValueError(f"{path}: the whole file's CRC32 does not fit 32 bits")
+    lens, raws, crcs, elems, expect, raw_sum = [], [], [], [], 0, 0
+    for i in range(k):
+        f = words[6 + 5 * i: 6 + 5 * (i + 1)]
+        off, ln, raw, c, e = num(f[0]), num(f[1]), num(f[2]), num(f[3], 16), num(f[4])
+        if off != expect or ln < 8 or off + ln >= M or ln > n_out - expect or raw > n_in - raw_sum:
+            raise ValueError(f"{path}: block {i + 1}'s entry does not fit (offset {off}, length {ln}, raw length {raw})")
+        if c >= 1 << 32:
+            raise ValueError(f"{path}: block {i + 1}'s CRC32 does not fit 32 bits")
+        if e not in (1, 2, 4, 8):
+            raise ValueError(f"{path}: block {i + 1}'s element size {e} is not 1, 2, 4 or 8")
+        lens.append(ln)
+        raws.append(raw)
+        crcs.append(c)
+        elems.append(e)
+        expect, raw_sum = expect + ln, raw_sum + raw
+    if expect != n_out or raw_sum != n_in:
+        raise ValueError(f"{path}: the blocks' lengths sum to {expect} / {raw_sum}, the header says {n_out} / {n_in}")
+    return lens, raws, crcs, elems
 
 
 def stats() -> dict:

@@ -67,6 +67,24 @@ using nlzm_host::decode_stream;
 
 void lower(char *v) { for (; *v; v++) *v = (char)(*v | 0x20); }
 
+// ---- -elem:E: the byte planes of a typed block undone on the host (the rule of nlzm_planes.h restated: y[j m + i] = x[i e + j], the tail as it is) ----
+void planes_undo(const uint8_t *y, uint8_t *x, uint64_t n, uint32_t e)
+{
+    const uint64_t m = n / e;
+    for (uint32_t j = 0; j < e; j++) for (uint64_t i = 0; i < m; i++) x[i * e + j] = y[j * m + i];
+    for (uint64_t t = e * m; t < n; t++) x[t] = y[t];
+}
+// does the sidecar index say NLZMIDX 3 (`c -elem:E` wrote it: blocks whose bytes are byte planes)?
+bool typed_index(const std::string &path)
+{
+    FILE *fi = fopen(path.c_str(), "rb");
+    if (!fi) return false;
+    unsigned ver = 0;
+    const bool typed = fscanf(fi, "NLZMIDX %u", &ver) == 1 && ver == 3;
+    fclose(fi);
+    return typed;
+}
+
 // ---- x: byte ranges of what a container holds (not in the reference) -----------------------------------------------------------
 struct ByteRange { uint64_t off, len; };
 
@@ -98,6 +116,7 @@ bool read_index(const std::string &path, Index &ix)
 int extract(const char *in_path, const char *out_path, const std::vector<ByteRange> &ranges, bool on_gpu)
 {
     if (FILE *probe = fopen(out_path, "rb")) { printf("Error: %s already exists\n", out_path); fclose(probe); return -1; }
+    if (typed_index(std::string(in_path) + ".idx")) { printf("Error: %s.idx is an NLZMIDX 3 index: x does not read the ranges of typed blocks (-elem:E); d undoes their byte planes\n", in_path); return -1; }
     FILE *fin = fopen(in_path, "rb");
     if (!fin) { printf("Error: %s file does not exist\n", in_path); return -1; }
     fseeko(fin, 0, SEEK_END);
@@ -266,6 +285,7 @@ int main(int argc, char **argv)
     bool on_gpu = false;                            // -gpu (not in the reference): d / t decode on the device; without it they are host-only and need none
     uint32_t cdc_bits = 0;                          // -cdc:B (not in the reference): c cuts the blocks by content on the device, 2^B bytes a block on average
     bool dedup = false;                             // -dedup (not in the reference): with -cdc:B, c does not compress a block again whose bytes an earlier block holds
+    uint32_t elem = 0;                              // -elem:E (not in the reference): c compresses every block's byte planes at element size E (NLZMIDX 3); d / t undo them
     uint32_t steps_k = 0;                           // -steps:K (not in the reference): d -gpu / t -gpu decode in steps of K frames per block
     std::vector<ByteRange> ranges;                  // -range:off:len (not in the reference): what x writes, in this order
     while (argc >= 2 && *argv[1] == '-') {
@@ -293,6 +313,9 @@ int main(int argc, char **argv)
             for (; ok && *p >= '0' && *p <= '9'; p++) { v = v * 10 + (unsigned)(*p - '0'); if (v > 30) ok = false; }
             if (!ok || *p || v < 10) { printf("Error: -cdc:B takes B from 10 to 30 (blocks of 2^B bytes on average)\n"); return -1; }
             cdc_bits = v;
+        } else if (!strncmp(arg, "elem:", 5)) {
+            if (strcmp(arg + 5, "2") && strcmp(arg + 5, "4") && strcmp(arg + 5, "8")) { printf("Error: -elem:E takes E of 2, 4 or 8 (the bytes of an element)\n"); return -1; }
+            elem = (uint32_t)(arg[5] - '0');
         } else if (!strcmp(arg, "dedup")) {
             dedup = true;
         } else if (!strcmp(arg, "verify")) {
@@ -331,11 +354,13 @@ int main(int argc, char **argv)
     const int cmd = argc >= 2 ? (argv[1][0] | 0x20) : 0;
     if (cdc_bits && (nblocks > 1 || ngpus)) { printf("Error: -cdc:B cuts the blocks by content; it does not go together with -blocks:k or -gpus:g\n"); return -1; }
     if (dedup && !cdc_bits) { printf("Error: -dedup skips the duplicates among the blocks that -cdc:B cuts; it needs -cdc:B\n"); return -1; }
+    if (elem && ngpus) { printf("Error: -elem:E filters the blocks of one GPU's container; it does not go together with -gpus:g\n"); return -1; }
+    if (elem) with_crc = true;                      // (the index holds the CRC32s of the RAW bytes: what d / t hold the undone planes against)
     if (ngpus && nblocks > 64) { nblocks = 64; printf("Blocks: %d (on each GPU: a launch holds no more)\n", nblocks); }
     if (steps_k && !(on_gpu && ((argc == 4 && cmd == 'd') || (argc == 3 && cmd == 't')))) { printf("Error: -steps:K is for d -gpu and t -gpu\n"); return -1; }
     if (argc == 4 && cmd == 'c') {
         if (FILE *probe = fopen(argv[3], "rb")) { printf("Error: %s already exists\n", argv[3]); fclose(probe); return -1; }
-        const bool one_stream = !ngpus && nblocks == 1 && !verify && !cdc_bits;      // (-verify and -cdc need the input whole: the one-call path)
+        const bool one_stream = !ngpus && nblocks == 1 && !verify && !cdc_bits && !elem;      // (-verify, -cdc and -elem need the input whole: the one-call path)
         std::vector<uint8_t> in;
         FILE *fin = nullptr;
         uint64_t in_size = 0;
@@ -363,6 +388,14 @@ int main(int argc, char **argv)
             if (crc == NLZM_HIP_E_CAPACITY) printf("Error: -cdc:%u cuts this input into %" PRIu64 " blocks, a container holds %u at most: raise B\n", cdc_bits, (uint64_t)ncuts + 1, nlzm::container::kMaxBlocks);
             else if (crc) printf("Error: %s\n", nlzm_hip_last_error());
             if (crc) { fclose(fout); remove(argv[3]); return -1; }
+            if (elem) {                                 // (whole elements a block: the cuts rounded down, equal ones dropped)
+                uint32_t kept = 0;
+                for (uint32_t i = 0; i < ncuts; i++) {
+                    const uint64_t c = cuts[i] / elem * elem;
+                    if (c && (!kept || c > cuts[kept - 1])) cuts[kept++] = c;
+                }
+                ncuts = kept;
+            }
             nstreams = ncuts + 1;
             for (uint32_t i = 0; i < nstreams; i++) {
                 const uint64_t lo = i ? cuts[i - 1] : 0, hi = i < ncuts ? cuts[i] : (uint64_t)in.size();
@@ -370,7 +403,8 @@ int main(int argc, char **argv)
             }
             printf("Blocks: %u (cut by content)\n", nstreams);
         } else if (!one_stream) {
-            const uint64_t per = (in.size() + nstreams - 1) / nstreams;
+            uint64_t per = (in.size() + nstreams - 1) / nstreams;
+            if (elem) per = (per + elem - 1) / elem * elem;      // (whole elements a block)
             for (uint32_t i = 0; i < nstreams; i++) {
                 const uint64_t lo = (uint64_t)i * per < in.size() ? (uint64_t)i * per : in.size(), hi = lo + per < in.size() ? lo + per : in.size();
                 boff.push_back(lo); braw.push_back(hi - lo);
@@ -439,14 +473,16 @@ int main(int argc, char **argv)
         }
         // room for the streams (a guaranteed bound: 9.7 GB at 65,536 blocks).  Not a vector: nothing is filled, and the pages behind the streams' end are never touched
         const size_t out_room = ngpus ? (size_t)nlzm_hip_compress_bound(in.size()) + (size_t)nstreams * (16 + 131072)
-                              : cdc_bits ? (size_t)nlzm_hip_compress_ranges_bound(nstreams, braw.data()) : (size_t)nlzm_hip_compress_blocks_bound(in.size(), nblocks);
+                              : cdc_bits || elem ? (size_t)nlzm_hip_compress_ranges_bound(nstreams, braw.data()) : (size_t)nlzm_hip_compress_blocks_bound(in.size(), nblocks);
         struct Room { uint8_t *p; size_t n; uint8_t *data() const { return p; } size_t size() const { return n; } ~Room() { free(p); } } out{ (uint8_t *)malloc(out_room ? out_room : 1), out_room };
         if (!out.data()) { printf("Error: no memory for %zu bytes of output\n", out_room); fclose(fout); remove(argv[3]); return -1; }
         std::vector<uint64_t> blen(nstreams);
         std::vector<int> devs;
         for (uint32_t d = 0; d < ngpus; d++) devs.push_back((int)d);
         if (dedup && nlzm_hip_set_option("dedup_ranges", 1)) { printf("Error: %s\n", nlzm_hip_last_error()); fclose(fout); remove(argv[3]); return -1; }
-        const int rc = cdc_bits ? nlzm_hip_compress_ranges(in.data(), in.size(), nstreams, boff.data(), braw.data(), hist_bits, out.data(), out.size(), blen.data(), &out_n)
+        const std::vector<uint8_t> elems(nstreams, (uint8_t)elem);
+        const int rc = elem ? nlzm_hip_compress_ranges_typed(in.data(), in.size(), nstreams, boff.data(), braw.data(), elems.data(), hist_bits, out.data(), out.size(), blen.data(), &out_n)
+                     : cdc_bits ? nlzm_hip_compress_ranges(in.data(), in.size(), nstreams, boff.data(), braw.data(), hist_bits, out.data(), out.size(), blen.data(), &out_n)
                      : ngpus ? nlzm_hip_compress_blocks_multi(devs.data(), ngpus, nblocks, in.data(), in.size(), hist_bits, out.data(), out.size(), blen.data(), &out_n)
                      : nblocks > 1 ? nlzm_hip_compress_blocks(in.data(), in.size(), nblocks, hist_bits, out.data(), out.size(), blen.data(), &out_n)
                                    : nlzm_hip_compress(in.data(), in.size(), hist_bits, out.data(), out.size(), &out_n);
@@ -466,6 +502,12 @@ int main(int argc, char **argv)
             struct timespec v0, v1;
             clock_gettime(CLOCK_MONOTONIC, &v0);
             int vrc = ngpus ? nlzm_hip_init(0) : 0;
+            if (!vrc && elem) {
+                // typed blocks: decoded through the typed entry point, which undoes the planes, and compared here (the blocks are the input, in order)
+                std::vector<uint8_t> back(in.size());
+                vrc = nlzm_hip_decompress_blocks_typed(out.data(), out_n, nstreams, blen.data(), braw.data(), elems.data(), back.data(), back.size(), nullptr, &decoded);
+                for (first = 0; !vrc && first < decoded && first < in.size() && back[first] == in[first];) first++;
+            } else
             if (!vrc) vrc = nlzm_hip_verify(out.data(), out_n, nstreams, nstreams > 1 ? blen.data() : nullptr, in.data(), in.size(), &first, &decoded);
             clock_gettime(CLOCK_MONOTONIC, &v1);
             if (vrc) { printf("Error: verify: %s\n", nlzm_hip_last_error()); fclose(fout); remove(argv[3]); return -1; }
@@ -490,17 +532,19 @@ int main(int argc, char **argv)
         }
         fwrite(out.data(), 1, (size_t)out_n, fout);
         fclose(fout);
-        if (nstreams > 1 || with_crc || cdc_bits) {
+        if (nstreams > 1 || with_crc || cdc_bits || elem) {
             // the block index, a sidecar: where every block's stream starts, how long it is and how many input bytes it holds.  The
             // streams stay self-delimiting -- the index only saves d/t the hop over every frame header of every block before the parallel decode can
             // start, and keeps the later blocks' boundaries when the container is damaged inside an earlier one.
             const std::string ip = std::string(argv[3]) + ".idx";
             if (FILE *fi = fopen(ip.c_str(), "wb")) {
-                if (with_crc) fprintf(fi, "NLZMIDX 2 %u %" PRIu64 " %" PRIu64 " %08X\n", nstreams, (uint64_t)in.size(), out_n, whole);
+                if (elem) fprintf(fi, "NLZMIDX 3 %u %" PRIu64 " %" PRIu64 " %08X\n", nstreams, (uint64_t)in.size(), out_n, whole);
+                else if (with_crc) fprintf(fi, "NLZMIDX 2 %u %" PRIu64 " %" PRIu64 " %08X\n", nstreams, (uint64_t)in.size(), out_n, whole);
                 else fprintf(fi, "NLZMIDX 1 %u %" PRIu64 " %" PRIu64 "\n", nstreams, (uint64_t)in.size(), out_n);
                 uint64_t off = 0;
                 for (uint32_t i = 0; i < nstreams; i++) {       // (each block's raw length its true one: the equal partition's, or the content's)
-                    if (with_crc) fprintf(fi, "%" PRIu64 " %" PRIu64 " %" PRIu64 " %08X\n", off, blen[i], braw[i], bcrc[i]);
+                    if (elem) fprintf(fi, "%" PRIu64 " %" PRIu64 " %" PRIu64 " %08X %u\n", off, blen[i], braw[i], bcrc[i], elem);
+                    else if (with_crc) fprintf(fi, "%" PRIu64 " %" PRIu64 " %" PRIu64 " %08X\n", off, blen[i], braw[i], bcrc[i]);
                     else fprintf(fi, "%" PRIu64 " %" PRIu64 " %" PRIu64 "\n", off, blen[i], braw[i]);
                     off += blen[i];
                 }
@@ -529,13 +573,14 @@ int main(int argc, char **argv)
         // decoded on a host thread each, written in order
         std::vector<Span> parts;
         std::vector<uint64_t> raws;                 // (by index) the input bytes every block holds
-        std::vector<uint32_t> idx_crcs;             // (by a version-2 index) every block's CRC32, and the whole file's
+        std::vector<uint8_t> idx_elems;             // (by a version-3 index) every block's element size: its bytes are byte planes
+        std::vector<uint32_t> idx_crcs;             // (by a version-2 or -3 index) every block's CRC32, and the whole file's
         uint32_t idx_whole = 0;
         bool idx_has_crc = false;
         size_t cut_tail = 0;
         bool by_index = false;
         auto find_parts = [&](bool use_index) {
-            parts.clear(); raws.clear(); idx_crcs.clear(); cut_tail = 0; by_index = false; idx_has_crc = false;
+            parts.clear(); raws.clear(); idx_crcs.clear(); idx_elems.clear(); cut_tail = 0; by_index = false; idx_has_crc = false;
             // the sidecar index of a block container, if it is there and fits the file: the blocks' boundaries without hopping over their frames
             const std::string ip = std::string(argv[2]) + ".idx";
             FILE *fi = use_index ? fopen(ip.c_str(), "rb") : nullptr;
@@ -545,24 +590,27 @@ int main(int argc, char **argv)
                 std::vector<Span> idx;
                 std::vector<uint64_t> idx_raw;
                 std::vector<uint32_t> idx_crc;
+                std::vector<uint8_t> idx_elem;
                 unsigned whole = 0;
-                bool ok = fscanf(fi, "NLZMIDX %u %u %llu %llu", &ver, &k, &n_in, &n_out) == 4 && (ver == 1 || ver == 2) && k >= 1 && k <= 4096 && n_out >= in.size();
-                if (ok && ver == 2) ok = fscanf(fi, "%x", &whole) == 1;         // (version 2: version 1 and a CRC32 behind the header's and every block's fields)
+                bool ok = fscanf(fi, "NLZMIDX %u %u %llu %llu", &ver, &k, &n_in, &n_out) == 4 && (ver >= 1 && ver <= 3) && k >= 1 && k <= 4096 && n_out >= in.size();
+                if (ok && ver >= 2) ok = fscanf(fi, "%x", &whole) == 1;         // (version 2: version 1 and a CRC32 behind the header's and every block's fields)
                 unsigned long long expect = 0, raw_sum = 0;
                 bool cut = false;
                 for (unsigned i = 0; ok && i < k && !cut; i++) {
                     unsigned long long off = 0, len = 0, raw = 0;
-                    unsigned bc = 0;
-                    ok = fscanf(fi, "%llu %llu %llu", &off, &len, &raw) == 3 && (ver == 1 || fscanf(fi, "%x", &bc) == 1) && off == expect && len >= 8 && off <= in.size() && raw <= n_in - raw_sum;
+                    unsigned bc = 0, be = 1;
+                    ok = fscanf(fi, "%llu %llu %llu", &off, &len, &raw) == 3 && (ver == 1 || fscanf(fi, "%x", &bc) == 1) && (ver < 3 || (fscanf(fi, "%u", &be) == 1 && (be == 1 || be == 2 || be == 4 || be == 8))) &&
+                         off == expect && len >= 8 && off <= in.size() && raw <= n_in - raw_sum;
                     if (ok && len > in.size() - off) { cut = true; break; }      // (the file ends inside this block: the ones in front of it are whole; no off + len, which can wrap)
                     // (a block's stream starts with its header and ends with its terminator, :1915-1921, :646-648)
                     if (ok) ok = in[off] == 0 && in[off + 1] >= 10 && in[off + 1] <= 28 && be32(&in[off + len - 4]) == 0;
-                    if (ok) { idx.push_back(Span{ in.data() + off, (size_t)len }); idx_raw.push_back(raw); idx_crc.push_back(bc); expect = off + len; raw_sum += raw; }
+                    if (ok) { idx.push_back(Span{ in.data() + off, (size_t)len }); idx_raw.push_back(raw); idx_crc.push_back(bc); idx_elem.push_back((uint8_t)be); expect = off + len; raw_sum += raw; }
                 }
                 fclose(fi);
                 if (ok && !idx.empty() && (cut || (expect == in.size() && n_out == in.size() && raw_sum == n_in))) {
                     parts = idx; raws = idx_raw; by_index = true;
-                    if (ver == 2) { idx_crcs = idx_crc; idx_whole = whole; idx_has_crc = true; }
+                    if (ver >= 2) { idx_crcs = idx_crc; idx_whole = whole; idx_has_crc = true; }
+                    if (ver == 3) idx_elems = idx_elem;
                     if (cut) cut_tail = in.size() - (size_t)expect;
                 } else printf("Note: %s does not fit this file; the blocks are found by their frame headers\n", ip.c_str());
             }
@@ -584,6 +632,8 @@ int main(int argc, char **argv)
                 pos += len;
             }
         };
+        const bool typed_idx = typed_index(std::string(argv[2]) + ".idx");
+        if (typed_idx && steps_k) { printf("Error: %s.idx is an NLZMIDX 3 index: -steps:K does not decode typed blocks (-elem:E)\n", argv[2]); if (fout) { fclose(fout); remove(argv[3]); } return -1; }
         if (on_gpu && nlzm_hip_init(0)) { printf("Error: %s\n", nlzm_hip_last_error()); if (fout) { fclose(fout); remove(argv[3]); } return -1; }
         int rc = 0;
         std::vector<uint32_t> got_crcs;             // what the blocks decoded to hash to (where a version-2 index gives CRCs to hold against)
@@ -591,6 +641,12 @@ int main(int argc, char **argv)
         bool out_on_device = false;                 // t -gpu with a version-2 index: decoded and hashed on the device, nothing came back
         for (int attempt = 0; attempt < 2; attempt++) {
             find_parts(attempt == 0);
+            if (typed_idx && !by_index) {           // (only the index says which blocks are byte planes, and of which element size)
+                printf("Error: %s.idx (NLZMIDX 3) does not fit this file, and without it the byte planes of its blocks cannot be undone\n", argv[2]);
+                if (fout) { fclose(fout); remove(argv[3]); }
+                return -1;
+            }
+            const bool typed = !idx_elems.empty();
             out.clear(); got_crcs.clear(); out_on_device = false; out_size = 0;
             rc = parts.empty() ? -3 : 0;
             bool index_wrong = false;               // a block did not decode to the bytes its index entry says it holds
@@ -639,7 +695,7 @@ int main(int argc, char **argv)
                     if (fout) { fflush(fout); if (ftruncate(fileno(fout), (off_t)total)) {} fseeko(fout, 0, SEEK_END); }
                     raws = raw; got_crcs = crcs; out_size = total; out_on_device = true;        // (nothing of the output is left on the host: its CRC32 is the blocks' combined)
                 }
-            } else if (!rc && on_gpu && idx_has_crc && cmd == 't') {
+            } else if (!rc && on_gpu && idx_has_crc && cmd == 't' && !typed) {
                 // nlzm_hip_check: decoded into a buffer on the device, every block bounded by its index entry, and hashed there
                 const uint32_t k = (uint32_t)parts.size();
                 std::vector<uint64_t> blen(k), raw(k);
@@ -677,7 +733,8 @@ int main(int argc, char **argv)
                     for (size_t i = 0; i < parts.size(); i++) total += raws[i];
                     bool room = true;
                     try { out.resize((size_t)total); } catch (const std::exception &) { room = false; }
-                    if (room) drc = nlzm_hip_decompress_blocks(parts[0].p, src_len, (uint32_t)parts.size(), blen.data(), raws.data(), out.data(), total, raw.data(), &total);
+                    if (room && typed) drc = nlzm_hip_decompress_blocks_typed(parts[0].p, src_len, (uint32_t)parts.size(), blen.data(), raws.data(), idx_elems.data(), out.data(), total, raw.data(), &total);
+                    else if (room) drc = nlzm_hip_decompress_blocks(parts[0].p, src_len, (uint32_t)parts.size(), blen.data(), raws.data(), out.data(), total, raw.data(), &total);
                     if (!room || drc == NLZM_HIP_E_CAPACITY || drc == NLZM_HIP_E_FORMAT || drc == NLZM_HIP_E_NOMEM) { index_wrong = true; drc = 0; std::vector<uint8_t>().swap(out); }
                 } else {
                     // no lengths anywhere in the format: a size pass, then the decode
@@ -713,6 +770,16 @@ int main(int argc, char **argv)
                 }
                 hb = hbs[0]; fb = fbs[0];
                 if (!index_wrong) printf("Blocks: %d\n", (int)parts.size());
+            }
+            if (typed && !on_gpu && !rc && !index_wrong) {
+                // host-only: the planes undone block by block, by the rule restated above; the CRC32s are the raw bytes', hashed below
+                std::vector<uint8_t> raw_bytes(out.size());
+                std::vector<std::thread> th;
+                uint64_t at = 0;
+                for (size_t i = 0; i < parts.size(); i++) { th.emplace_back([&, i, at] { planes_undo(out.data() + at, raw_bytes.data() + at, raws[i], idx_elems[i]); }); at += raws[i]; }
+                for (auto &t : th) t.join();
+                out.swap(raw_bytes);
+                got_crcs.clear();
             }
             if (!(by_index && (index_wrong || rc))) break;
             // the index passed its checks and still does not describe these streams (stale, or of another file): the frame headers decide
@@ -772,6 +839,7 @@ int main(int argc, char **argv)
                "\t-blocks:k = (this build) compress k independent blocks, 1 to 65536: as many at once as a launch holds (64), more of them\n"
                "\t            in sets one after another; d/t read the streams back to back\n"
                "\t-cdc:B = (this build) c cuts the blocks by content on the GPU, 2^B bytes on average (B 10 to 30): an edit changes the blocks around it only\n"
+               "\t-elem:E = (this build) c compresses every block's byte planes at element size E (2, 4 or 8), alone or with -blocks:k / -cdc:B, and writes NLZMIDX 3; d / t undo them\n"
                "\t-dedup = (this build) with -cdc:B: a block whose bytes an earlier block holds is not compressed again, its stream is a copy (the same container)\n"
                "\t-gpus:g = (this build) the blocks on GPUs 0..g-1 of this node, -blocks:k of them on each (64 at most)\n"
                "\t-verify = (this build) c decodes what it wrote on the GPU, one workgroup per stream, compares it with the input\n"
