@@ -4,6 +4,7 @@
 // `d`/`t` decode on the host (the decoder is a serial byte-copy machine and stays
 // on the CPU: SURVEY.md 8f-1); `h` prints the CRC32; `x` (not in the reference) writes byte ranges of what
 // a block container holds, reading only the blocks they need (host decoder, or nlzm_hip_read_ranges with -gpu).
+// main() reads the flags and hands over to one function per command; the sidecar index is nlzm_index.h's.
 //
 // Messages, flag handling and exit codes follow the reference:
 //   flags lower-cased, leading '-' stripped, -window:N clamped to [15,28]   :2074-2092
@@ -18,6 +19,7 @@
 #include <unistd.h>
 
 #include <exception>
+#include <memory>
 #include <thread>
 #include <string>
 #include <vector>
@@ -26,6 +28,7 @@
 #include "nlzm_host_decode.h"
 #include "nlzm_read_plan.h"
 #include "nlzm_container_plan.h"       // (kMaxBlocks)
+#include "nlzm_index.h"
 
 namespace {
 
@@ -58,12 +61,50 @@ bool slurp(const char *path, std::vector<uint8_t> &buf)
     fclose(f);
     return ok;
 }
+bool refuse_existing(const char *path)
+{
+    FILE *probe = fopen(path, "rb");
+    if (probe) { printf("Error: %s already exists\n", path); fclose(probe); }
+    return probe != nullptr;
+}
+int hip_error(const char *what = "") { printf("Error: %s%s\n", what, nlzm_hip_last_error()); return -1; }
+double seconds(const timespec &a, const timespec &b) { return (double)(b.tv_sec - a.tv_sec) + 1e-9 * (double)(b.tv_nsec - a.tv_nsec); }
+
+// The output file of c and d.  Whatever way the command ends, the file is removed again unless done() said that it stays.
+struct OutFile {
+    const char *path = nullptr;
+    FILE *f = nullptr;
+    bool open(const char *p) { path = p; f = fopen(p, "wb"); return f != nullptr; }
+    void done() { if (f) fclose(f); f = nullptr; }
+    ~OutFile() { if (f) { fclose(f); remove(path); } }
+};
+
+// one host thread per block, all of them joined
+template <class Fn>
+void for_each_block(size_t k, Fn fn)
+{
+    std::vector<std::thread> th;
+    for (size_t i = 0; i < k; i++) th.emplace_back([&fn, i] { fn(i); });
+    for (auto &t : th) t.join();
+}
+
+// digits and nothing else; a number over `max` is refused, not saturated
+bool parse_uint(const char *&p, unsigned long long max, unsigned long long &v)
+{
+    if (*p < '0' || *p > '9') return false;
+    for (v = 0; *p >= '0' && *p <= '9'; p++) {
+        const unsigned long long d = (unsigned long long)(*p - '0');
+        if (v > (max - d) / 10) return false;
+        v = v * 10 + d;
+    }
+    return true;
+}
 
 // ---- host decoder: decode_file (NLZM.cpp:1912-2039), shared with the device decoder's test harness ----------
 using nlzm_host::Span;
-using nlzm_host::be32;
 using nlzm_host::stream_length;
 using nlzm_host::decode_stream;
+using nlzm::index::Index;
 
 void lower(char *v) { for (; *v; v++) *v = (char)(*v | 0x20); }
 
@@ -74,83 +115,543 @@ void planes_undo(const uint8_t *y, uint8_t *x, uint64_t n, uint32_t e)
     for (uint32_t j = 0; j < e; j++) for (uint64_t i = 0; i < m; i++) x[i * e + j] = y[j * m + i];
     for (uint64_t t = e * m; t < n; t++) x[t] = y[t];
 }
-// does the sidecar index say NLZMIDX 3 (`c -elem:E` wrote it: blocks whose bytes are byte planes)?
-bool typed_index(const std::string &path)
-{
-    FILE *fi = fopen(path.c_str(), "rb");
-    if (!fi) return false;
-    unsigned ver = 0;
-    const bool typed = fscanf(fi, "NLZMIDX %u", &ver) == 1 && ver == 3;
-    fclose(fi);
-    return typed;
-}
 
-// ---- x: byte ranges of what a container holds (not in the reference) -----------------------------------------------------------
 struct ByteRange { uint64_t off, len; };
+struct Options {
+    uint32_t hist_bits = 22;                        // :2071
+    uint32_t nblocks = 1;                           // -blocks:k (not in the reference): k independent streams, back to back
+    uint32_t ngpus = 0;                             // -gpus:g (not in the reference): the blocks on g GPUs of this node, -blocks:k on each
+    bool verify = false;                            // -verify (not in the reference): c decodes what it wrote on the device and compares it with the input
+    bool with_crc = false;                          // -crc (not in the reference): c keeps every block's CRC32, hashed on the device, in the index (NLZMIDX 2); d / t check them
+    bool on_gpu = false;                            // -gpu (not in the reference): d / t decode on the device; without it they are host-only and need none
+    uint32_t cdc_bits = 0;                          // -cdc:B (not in the reference): c cuts the blocks by content on the device, 2^B bytes a block on average
+    bool dedup = false;                             // -dedup (not in the reference): with -cdc:B, c does not compress a block again whose bytes an earlier block holds
+    uint32_t elem = 0;                              // -elem:E (not in the reference): c compresses every block's byte planes at element size E (NLZMIDX 3); d / t undo them
+    uint32_t steps_k = 0;                           // -steps:K (not in the reference): d -gpu / t -gpu decode in steps of K frames per block
+    std::vector<ByteRange> ranges;                  // -range:off:len (not in the reference): what x writes, in this order
+};
 
-// The sidecar index as `x` needs it: the file itself is not consulted (it may be cut off behind the blocks a range needs), so the checks are
-// the structural ones -- no sum that wraps, offsets back to back, lengths summing to the header's n_out and raw lengths to its n_in.
-struct Index { std::vector<uint64_t> off, len, raw; std::vector<uint32_t> crc; bool has_crc = false; };
-bool read_index(const std::string &path, Index &ix)
+// What each reader takes of an index.  d / t: every version, fields behind the last block let pass, 4096 blocks (c -blocks:k writes up to 65,536:
+// DESIGN.md section 17).  x: versions 1 and 2 -- it does not read typed blocks --, 65,536 blocks, nothing behind the last block.
+const nlzm::index::Accept kDecodeTakes{ 3, 4096, true }, kExtractTakes{ 2, nlzm::container::kMaxBlocks, false };
+
+// ---- c ---------------------------------------------------------------------------------------------------------------------------------
+// the reference's summary (:1755-1759): sizes of its own structures for this window
+void print_summary(uint64_t in_size, uint32_t hist_bits, uint32_t nstreams)
 {
-    FILE *fi = fopen(path.c_str(), "rb");
-    if (!fi) return false;
-    unsigned ver = 0, k = 0, whole = 0;
-    unsigned long long n_in = 0, n_out = 0, expect = 0, raw_sum = 0;
-    bool ok = fscanf(fi, "NLZMIDX %u %u %llu %llu", &ver, &k, &n_in, &n_out) == 4 && (ver == 1 || ver == 2) && k >= 1 && k <= 65536;
-    if (ok && ver == 2) ok = fscanf(fi, "%x", &whole) == 1;
-    for (unsigned i = 0; ok && i < k; i++) {
-        unsigned long long off = 0, len = 0, raw = 0;
-        unsigned bc = 0;
-        ok = fscanf(fi, "%llu %llu %llu", &off, &len, &raw) == 3 && (ver == 1 || fscanf(fi, "%x", &bc) == 1) && off == expect && len >= 8 && len <= n_out - expect &&
-             raw <= n_in - raw_sum;
-        if (ok) { ix.off.push_back(off); ix.len.push_back(len); ix.raw.push_back(raw); ix.crc.push_back(bc); expect += len; raw_sum += raw; }
-    }
-    char extra[2];
-    if (ok && fscanf(fi, "%1s", extra) == 1) ok = false;       // (fields behind the last block's: not this index)
-    fclose(fi);
-    ix.has_crc = ver == 2;
-    return ok && expect == n_out && raw_sum == n_in;
+    uint32_t hb, fb, cs, feed;
+    nlzm_hip_geometry(in_size, hist_bits, &hb, &fb, &cs, &feed);
+    const uint32_t c1 = hb < 15 ? 15 : (hb > 17 ? 17 : hb), c2 = hb < 16 ? 16 : (hb > 20 ? 20 : hb), c3 = hb < 16 ? 16 : (hb > 22 ? 22 : hb);
+    const uint64_t mf = (4ull << 12) + (8ull << (12 + c1 - 15)) + (4ull << (13 + c2 - 16)) + (8ull << hb) + (4ull << (15 + c3 - 16));
+    printf("Model: %d KB\n", 2);
+    printf("Parser: %d KB\n", 65);
+    printf("Dictionary: %d KB\n", (int)(((1ull << hb) + 1023) >> 10));
+    printf("Frame: %d KB\n", (int)(((1u << fb) + 1023) >> 10));
+    printf("Dictionary search: %d KB\n", (int)((mf + 1023) >> 10));
+    if (nstreams > 1)
+        printf("Note: %u independent streams are written back to back; this program's d/t read them, the reference's d "
+               "stops after the first\n", nstreams);
+    printf("Working...\r");
 }
 
-int extract(const char *in_path, const char *out_path, const std::vector<ByteRange> &ranges, bool on_gpu)
+// The block index, a sidecar: where every block's stream starts, how long it is and how many input bytes it holds.  The
+// streams stay self-delimiting -- the index only saves d/t the hop over every frame header of every block before the parallel decode can
+// start, and keeps the later blocks' boundaries when the container is damaged inside an earlier one.
+void write_index(const char *out_path, const Index &ix)
 {
-    if (FILE *probe = fopen(out_path, "rb")) { printf("Error: %s already exists\n", out_path); fclose(probe); return -1; }
-    if (typed_index(std::string(in_path) + ".idx")) { printf("Error: %s.idx is an NLZMIDX 3 index: x does not read the ranges of typed blocks (-elem:E); d undoes their byte planes\n", in_path); return -1; }
+    const std::string ip = std::string(out_path) + ".idx";
+    if (FILE *fi = fopen(ip.c_str(), "wb")) {
+        nlzm::index::write(fi, ix);
+        fclose(fi);
+        printf("Block index: %s\n", ip.c_str());
+    }
+}
+
+// read, uploaded and compressed piece by piece (nlzm_hip_feed_*): the file is never whole in host memory
+int compress_one_stream(const Options &o, const char *in_path, const char *out_path)
+{
     FILE *fin = fopen(in_path, "rb");
     if (!fin) { printf("Error: %s file does not exist\n", in_path); return -1; }
     fseeko(fin, 0, SEEK_END);
-    const uint64_t file_size = (uint64_t)ftello(fin);
-    Index ix;
-    std::vector<uint8_t> whole_file;                // (without an index: the container is read whole and split by its frame headers)
-    const bool by_index = read_index(std::string(in_path) + ".idx", ix);
+    const uint64_t in_size = (uint64_t)ftello(fin);
+    fseeko(fin, 0, SEEK_SET);
+    OutFile fout;
+    if (!fout.open(out_path)) { printf("Error: %s file does not exist\n", out_path); fclose(fin); return -1; }
+    if (nlzm_hip_init(0)) return hip_error();
+    print_summary(in_size, o.hist_bits, 1);
+    uint64_t out_n = 0;
+    struct timespec w0, w1;
+    clock_gettime(CLOCK_MONOTONIC, &w0);
+    // the reference's loop in big steps: read a piece, hand it over, write the frames that are finished (:1774-1778, :1853, :1870-1885)
+    std::vector<uint8_t> piece(16u << 20), obuf(16u << 20);
+    uint32_t crc = 0;
+    int rc = nlzm_hip_feed_begin(in_size, o.hist_bits);
+    auto drain = [&]() {
+        for (uint64_t got = 1; !rc && got;) {
+            rc = nlzm_hip_feed_output(obuf.data(), obuf.size(), &got);
+            if (!rc && got) { fwrite(obuf.data(), 1, (size_t)got, fout.f); out_n += got; }
+        }
+    };
+    for (uint64_t done = 0; !rc && done < in_size;) {
+        const size_t m = (size_t)(in_size - done < piece.size() ? in_size - done : piece.size());
+        if (fread(piece.data(), 1, m, fin) != m) { printf("Error: %s could not be read\n", in_path); rc = -1; break; }
+        if (!o.with_crc) crc = crc_calc(piece.data(), m, crc);
+        rc = nlzm_hip_feed(piece.data(), m);
+        done += m;
+        drain();
+        printf("Working... %" PRIu64 " -> %" PRIu64 "\r", done, out_n);
+        fflush(stdout);
+    }
+    if (!rc) rc = nlzm_hip_feed_finish();
+    drain();
+    if (!rc && o.with_crc) rc = nlzm_hip_feed_input_crc32(&crc);      // (the input is whole in HBM and nowhere on the host: hashed where it lies)
+    nlzm_hip_feed_end();
+    fclose(fin);
+    clock_gettime(CLOCK_MONOTONIC, &w1);
+    if (rc) return rc != -1 ? hip_error() : -1;
+    fout.done();
+    if (o.with_crc) {
+        Index ix;
+        ix.version = 2; ix.n_in = in_size; ix.n_out = out_n; ix.whole = crc;
+        ix.off = { 0 }; ix.len = { out_n }; ix.raw = { in_size }; ix.crc = { crc };
+        write_index(out_path, ix);
+    }
+    printf("Working... %" PRIu64 " -> %" PRIu64 "\n", in_size, out_n);
+    printf("Done (input CRC32 %X, %.2f sec)\n", crc, seconds(w0, w1));
+    nlzm_hip_shutdown();
+    return 0;
+}
+
+// every block's bytes of the input: cut by content on the device (-cdc:B), or the equal partition; with -elem:E, whole elements a block
+bool partition(const Options &o, const std::vector<uint8_t> &in, std::vector<uint64_t> &boff, std::vector<uint64_t> &braw)
+{
+    if (!o.cdc_bits) {
+        const uint32_t nstreams = o.ngpus ? o.ngpus * o.nblocks : o.nblocks;
+        uint64_t per = (in.size() + nstreams - 1) / nstreams;
+        if (o.elem) per = (per + o.elem - 1) / o.elem * o.elem;
+        for (uint32_t i = 0; i < nstreams; i++) {
+            const uint64_t lo = (uint64_t)i * per < in.size() ? (uint64_t)i * per : in.size(), hi = lo + per < in.size() ? lo + per : in.size();
+            boff.push_back(lo); braw.push_back(hi - lo);
+        }
+        return true;
+    }
+    // the cut points from the device, with the default lengths: 2^(B - 2) .. 2^(B + 2) bytes a block (2^31 at most)
+    const uint64_t min_len = 1ull << (o.cdc_bits - 2), max_len = o.cdc_bits + 2 > 31 ? 1ull << 31 : 1ull << (o.cdc_bits + 2);
+    std::vector<uint64_t> cuts(nlzm::container::kMaxBlocks - 1);
+    uint32_t ncuts = 0;
+    const int rc = nlzm_hip_cut_points(in.data(), in.size(), o.cdc_bits, min_len, max_len, cuts.data(), (uint32_t)cuts.size(), &ncuts);
+    if (rc == NLZM_HIP_E_CAPACITY) printf("Error: -cdc:%u cuts this input into %" PRIu64 " blocks, a container holds %u at most: raise B\n", o.cdc_bits, (uint64_t)ncuts + 1, nlzm::container::kMaxBlocks);
+    else if (rc) hip_error();
+    if (rc) return false;
+    if (o.elem) {                                   // (the cuts rounded down, equal ones dropped)
+        uint32_t kept = 0;
+        for (uint32_t i = 0; i < ncuts; i++) {
+            const uint64_t c = cuts[i] / o.elem * o.elem;
+            if (c && (!kept || c > cuts[kept - 1])) cuts[kept++] = c;
+        }
+        ncuts = kept;
+    }
+    for (uint32_t i = 0; i <= ncuts; i++) {
+        const uint64_t lo = i ? cuts[i - 1] : 0, hi = i < ncuts ? cuts[i] : (uint64_t)in.size();
+        boff.push_back(lo); braw.push_back(hi - lo);
+    }
+    printf("Blocks: %u (cut by content)\n", ncuts + 1);
+    return true;
+}
+
+// the input whole, one call: blocks, -verify, -crc, the index (-verify, -cdc and -elem need the input whole, so one stream with them comes here too)
+int compress_container(const Options &o, const char *in_path, const char *out_path)
+{
+    const uint32_t ngpus = o.ngpus, nblocks = o.nblocks, elem = o.elem;
+    std::vector<uint8_t> in;
+    if (!slurp(in_path, in)) { printf("Error: %s file does not exist\n", in_path); return -1; }
+    OutFile fout;
+    if (!fout.open(out_path)) { printf("Error: %s file does not exist\n", out_path); return -1; }
+    if (!ngpus && nlzm_hip_init(0)) return hip_error();
+    std::vector<uint64_t> boff, braw;
+    if (!partition(o, in, boff, braw)) return -1;
+    const uint32_t nstreams = (uint32_t)boff.size();
+    print_summary(in.size(), o.hist_bits, nstreams);
+    uint64_t out_n = 0;
+    struct timespec w0, w1;
+    clock_gettime(CLOCK_MONOTONIC, &w0);
+    // room for the streams (a guaranteed bound: 9.7 GB at 65,536 blocks).  Not a vector: nothing is filled, and the pages behind the streams' end are never touched
+    const size_t out_room = ngpus ? (size_t)nlzm_hip_compress_bound(in.size()) + (size_t)nstreams * (16 + 131072)
+                          : o.cdc_bits || elem ? (size_t)nlzm_hip_compress_ranges_bound(nstreams, braw.data()) : (size_t)nlzm_hip_compress_blocks_bound(in.size(), nblocks);
+    struct Room { uint8_t *p; size_t n; uint8_t *data() const { return p; } size_t size() const { return n; } ~Room() { free(p); } } out{ (uint8_t *)malloc(out_room ? out_room : 1), out_room };
+    if (!out.data()) { printf("Error: no memory for %zu bytes of output\n", out_room); return -1; }
+    std::vector<uint64_t> blen(nstreams);
+    std::vector<int> devs;
+    for (uint32_t d = 0; d < ngpus; d++) devs.push_back((int)d);
+    if (o.dedup && nlzm_hip_set_option("dedup_ranges", 1)) return hip_error();
+    const std::vector<uint8_t> elems(nstreams, (uint8_t)elem);
+    const int rc = elem ? nlzm_hip_compress_ranges_typed(in.data(), in.size(), nstreams, boff.data(), braw.data(), elems.data(), o.hist_bits, out.data(), out.size(), blen.data(), &out_n)
+                 : o.cdc_bits ? nlzm_hip_compress_ranges(in.data(), in.size(), nstreams, boff.data(), braw.data(), o.hist_bits, out.data(), out.size(), blen.data(), &out_n)
+                 : ngpus ? nlzm_hip_compress_blocks_multi(devs.data(), ngpus, nblocks, in.data(), in.size(), o.hist_bits, out.data(), out.size(), blen.data(), &out_n)
+                 : nblocks > 1 ? nlzm_hip_compress_blocks(in.data(), in.size(), nblocks, o.hist_bits, out.data(), out.size(), blen.data(), &out_n)
+                               : nlzm_hip_compress(in.data(), in.size(), o.hist_bits, out.data(), out.size(), &out_n);
+    clock_gettime(CLOCK_MONOTONIC, &w1);
+    if (rc) return hip_error();
+    if (nstreams == 1) blen[0] = out_n;
+    if (o.dedup) {          // (the finder's counters of the call: the blocks that were another's copy, and their bytes)
+        uint64_t distinct = nstreams, dup_bytes = 0;
+        (void)nlzm_hip_get_counter("dedup_distinct", &distinct);
+        (void)nlzm_hip_get_counter("dedup_dup_bytes", &dup_bytes);
+        printf("Duplicates: %" PRIu64 " of %u blocks (%" PRIu64 " bytes) not compressed again\n", (uint64_t)nstreams - distinct, nstreams, dup_bytes);
+    }
+    if (o.verify) {
+        // the stream(s) decoded on the device, one workgroup each, and compared there with the input; neither comes back to the host
+        uint64_t first = 0, decoded = 0;
+        struct timespec v0, v1;
+        clock_gettime(CLOCK_MONOTONIC, &v0);
+        int vrc = ngpus ? nlzm_hip_init(0) : 0;
+        if (!vrc && elem) {
+            // typed blocks: decoded through the typed entry point, which undoes the planes, and compared here (the blocks are the input, in order)
+            std::vector<uint8_t> back(in.size());
+            vrc = nlzm_hip_decompress_blocks_typed(out.data(), out_n, nstreams, blen.data(), braw.data(), elems.data(), back.data(), back.size(), nullptr, &decoded);
+            for (first = 0; !vrc && first < decoded && first < in.size() && back[first] == in[first];) first++;
+        } else
+        if (!vrc) vrc = nlzm_hip_verify(out.data(), out_n, nstreams, nstreams > 1 ? blen.data() : nullptr, in.data(), in.size(), &first, &decoded);
+        clock_gettime(CLOCK_MONOTONIC, &v1);
+        if (vrc) return hip_error("verify: ");
+        if (!NLZM_HIP_VERIFY_EQUAL(first, decoded, (uint64_t)in.size())) {
+            if (first < in.size() && first < decoded) printf("Verify FAILED: the stream decodes to something else from offset %" PRIu64 "; %s removed\n", first, out_path);
+            else printf("Verify FAILED: the stream decodes to %" PRIu64 " bytes, the input has %" PRIu64 " (equal up to offset %" PRIu64 "); %s removed\n", decoded, (uint64_t)in.size(), first, out_path);
+            return -3;
+        }
+        uint64_t dev_us = 0;
+        (void)nlzm_hip_get_counter("decode_us", &dev_us);
+        printf("Verified (%.2f sec, %.2f of them decoding on the device)\n", seconds(v0, v1), 1e-6 * (double)dev_us);
+    }
+    // -crc: every block's CRC32 from the device, on a re-upload of the input as -verify makes one; the whole file's is their combination
+    std::vector<uint32_t> bcrc(nstreams, 0);
+    uint32_t whole = 0;
+    if (o.with_crc) {
+        int crc_rc = ngpus ? nlzm_hip_init(0) : 0;
+        if (!crc_rc) crc_rc = nlzm_hip_crc32_ranges(in.data(), in.size(), nstreams, boff.data(), braw.data(), bcrc.data());
+        if (crc_rc) return hip_error("crc: ");
+        for (uint32_t i = 0; i < nstreams; i++) whole = nlzm_hip_crc32_combine(whole, bcrc[i], braw[i]);
+    }
+    fwrite(out.data(), 1, (size_t)out_n, fout.f);
+    fout.done();
+    if (nstreams > 1 || o.with_crc || o.cdc_bits || elem) {
+        Index ix;                                   // (each block's raw length its true one: the equal partition's, or the content's)
+        ix.version = elem ? 3 : o.with_crc ? 2 : 1; ix.n_in = in.size(); ix.n_out = out_n; ix.whole = whole;
+        ix.off.assign(nstreams, 0); ix.len = blen; ix.raw = braw; ix.crc = bcrc; ix.elem = elems;
+        for (uint32_t i = 1; i < nstreams; i++) ix.off[i] = ix.off[i - 1] + blen[i - 1];
+        write_index(out_path, ix);
+    }
+    printf("Working... %" PRIu64 " -> %" PRIu64 "\n", (uint64_t)in.size(), out_n);
+    printf("Done (input CRC32 %X, %.2f sec)\n", o.with_crc ? whole : crc_calc(in.data(), in.size(), 0), seconds(w0, w1));
+    nlzm_hip_shutdown();
+    return 0;
+}
+
+// ---- d / t -----------------------------------------------------------------------------------------------------------------------------
+// The streams of what d / t read -- one (the reference's format), or several back to back (block mode) -- and what the index says of them.
+struct Found {
+    std::vector<Span> parts;
+    std::vector<uint64_t> blen;                     // their lengths
+    bool by_index = false;                          // the boundaries are the index's; otherwise found by hopping over the frames
+    Index ix;                                       // (by index) the index: the parts are its first entries -- all of them, unless the container is cut off
+    size_t cut_tail = 0;                            // the container is cut off inside the block behind the last of `parts`: so many bytes of it are there
+    uint64_t src_len() const { return (uint64_t)(parts.back().p + parts.back().n - parts[0].p); }
+};
+
+Found find_parts(const std::vector<uint8_t> &in, const Index *ix, const char *in_path)
+{
+    Found f;
+    // the sidecar index of a block container, if it is there and fits the file: the blocks' boundaries without hopping over their frames
+    if (ix && ix->present) {
+        const size_t n = nlzm::index::fits_file(*ix, kDecodeTakes, in.data(), in.size(), f.cut_tail);
+        for (size_t i = 0; i < n; i++) f.parts.push_back(Span{ in.data() + ix->off[i], (size_t)ix->len[i] });
+        if (n) { f.by_index = true; f.ix = *ix; }
+        else printf("Note: %s.idx does not fit this file; the blocks are found by their frame headers\n", in_path);
+    }
+    for (size_t pos = 0; !f.by_index && pos < in.size();) {
+        const Span rest{ in.data() + pos, in.size() - pos };
+        const size_t len = stream_length(rest);
+        if (!len) {
+            // what follows is not a stream: the reference stops at the first terminator (:646-648) and so do we;
+            // a container that is cut off inside its first stream is malformed
+            if (f.parts.empty()) break;
+            // a further stream header (:1915-1921: hist_bits, frame_bits, both big-endian 16-bit) with a frame that is cut off:
+            // the complete streams are decoded and written, and the exit status says that the container was cut
+            const bool header = rest.n >= 4 && rest.p[0] == 0 && rest.p[1] >= 10 && rest.p[1] <= 28 && rest.p[2] == 0 && rest.p[3] >= 12 && rest.p[3] <= 20;
+            if (header) f.cut_tail = rest.n;
+            else printf("Note: %zu bytes after the last stream ignored\n", rest.n);
+            break;
+        }
+        f.parts.push_back(Span{ rest.p, len });
+        pos += len;
+    }
+    for (const Span &s : f.parts) f.blen.push_back(s.n);
+    return f;
+}
+
+// What one way of decoding made of the parts.  failed: an error that is no verdict on the streams, already printed; d / t end with -1.
+struct Decoded {
+    bool failed = false;
+    int rc = 0;                                     // the streams are malformed
+    bool index_wrong = false;                       // a block did not decode to the bytes its index entry says it holds
+    std::vector<uint8_t> out;
+    std::vector<uint32_t> got_crcs;                 // what the blocks decoded to hash to, where the decode hashed them
+    uint64_t out_size = 0;
+    bool out_on_device = false;                     // nothing of the output is on the host: out_size and got_crcs say what it was
+    uint32_t hb = 0, fb = 0;
+};
+// a device call's answer: a malformed stream is the streams' fault, anything else an error
+void device_verdict(Decoded &r, int drc, const Found &f)
+{
+    if (drc == NLZM_HIP_E_FORMAT) r.rc = -7;
+    else if (drc) { hip_error(); r.failed = true; }
+    r.hb = f.parts[0].p[1]; r.fb = f.parts[0].p[3];
+}
+
+// -gpu -steps:K: the decode in steps of K frames per block (nlzm_hip_decode_*): after every step each block's new bytes are fetched, hashed and --
+// d -- written at the block's offset, so the host holds one step's output at a time
+Decoded decode_in_steps(Found &f, uint32_t steps_k, FILE *fout)
+{
+    Decoded r;
+    const uint32_t k = (uint32_t)f.parts.size();
+    std::vector<uint64_t> raw(k), at(k, 0), done(k, 0), had(k, 0);
+    const uint64_t src_len = f.src_len();
+    uint64_t total = 0, launches = 0;
+    int drc = 0;
+    if (f.by_index) raw = f.ix.raw;
+    else drc = nlzm_hip_decompress_blocks(f.parts[0].p, src_len, k, f.blen.data(), nullptr, nullptr, 0, raw.data(), &total);      // (no lengths anywhere in the format: a size pass)
+    for (uint32_t i = 1; i < k; i++) at[i] = at[i - 1] + raw[i - 1];
+    if (!drc) drc = nlzm_hip_decode_begin(f.parts[0].p, src_len, k, f.blen.data(), raw.data(), 0);
+    std::vector<uint32_t> crcs(k, 0);
+    std::vector<uint8_t> piece;
+    int finished = 0;
+    bool open = !drc;
+    while (!drc && !finished) {
+        drc = nlzm_hip_decode_step(steps_k, nullptr, done.data(), &finished, nullptr);
+        if (drc) { open = false; break; }           // (a failing step has closed the set)
+        for (uint32_t i = 0; i < k && !drc; i++) {
+            const uint64_t n = done[i] - had[i];
+            if (!n) continue;
+            piece.resize((size_t)n);
+            drc = nlzm_hip_decode_fetch(at[i] + had[i], n, piece.data());
+            if (drc) break;
+            crcs[i] = crc_calc(piece.data(), n, crcs[i]);
+            if (fout) { fseeko(fout, (off_t)(at[i] + had[i]), SEEK_SET); fwrite(piece.data(), 1, (size_t)n, fout); }
+            had[i] = done[i];
+        }
+    }
+    if (!drc) { (void)nlzm_hip_get_counter("decode_steps", &launches); drc = nlzm_hip_decode_finish(nullptr, &total); open = false; }
+    if (open) nlzm_hip_decode_abandon();
+    if (f.by_index && (drc == NLZM_HIP_E_CAPACITY || drc == NLZM_HIP_E_FORMAT || drc == NLZM_HIP_E_NOMEM)) { r.index_wrong = true; drc = 0; }
+    device_verdict(r, drc, f);
+    if (r.failed) return r;
+    // (a decode that did not come to its end leaves nothing of what its steps wrote: the one-call path writes nothing then either)
+    if ((r.index_wrong || r.rc) && fout) { fflush(fout); if (ftruncate(fileno(fout), 0)) {} fseeko(fout, 0, SEEK_SET); }
+    if (!r.index_wrong && !r.rc) {
+        if (k > 1) printf("Blocks: %d\n", (int)k);
+        printf("Steps: %u frames, %" PRIu64 " launches\n", steps_k, launches);
+        if (fout) { fflush(fout); if (ftruncate(fileno(fout), (off_t)total)) {} fseeko(fout, 0, SEEK_END); }
+        f.ix.raw = raw; r.got_crcs = crcs; r.out_size = total; r.out_on_device = true;        // (the output's CRC32 is the blocks' combined)
+    }
+    return r;
+}
+
+// t -gpu by an index with CRC32s (nlzm_hip_check): decoded into a buffer on the device, every block bounded by its index entry, and hashed there
+Decoded check_on_device(const Found &f)
+{
+    Decoded r;
+    const uint32_t k = (uint32_t)f.parts.size();
+    std::vector<uint64_t> raw(k);
+    uint32_t first_bad = k;
+    r.got_crcs.assign(k, 0);
+    int drc = nlzm_hip_check(f.parts[0].p, f.src_len(), k, f.blen.data(), f.ix.raw.data(), f.ix.crc.data(), &first_bad, r.got_crcs.data());
+    if (!drc && first_bad < k) {
+        // a wrong length or a wrong CRC?  The blocks' own lengths say (a size pass; only a container that fails pays for it)
+        uint64_t total = 0;
+        drc = nlzm_hip_decompress_blocks(f.parts[0].p, f.src_len(), k, f.blen.data(), nullptr, nullptr, 0, raw.data(), &total);
+        for (uint32_t i = 0; !drc && i < k; i++) if (raw[i] != f.ix.raw[i]) r.index_wrong = true;
+    }
+    if (drc == NLZM_HIP_E_NOMEM) { r.index_wrong = true; drc = 0; }
+    device_verdict(r, drc, f);
+    if (r.failed) return r;
+    for (uint32_t i = 0; i < k; i++) r.out_size += f.ix.raw[i];
+    r.out_on_device = true;
+    if (!r.index_wrong && !r.rc && k > 1) printf("Blocks: %d\n", (int)k);
+    if (r.index_wrong || r.rc) { r.out_size = 0; r.got_crcs.clear(); }
+    return r;
+}
+
+// -gpu: all blocks at once on the device, one workgroup each; boundaries from the parts, raw lengths from the index where it gave them
+Decoded decode_on_device(const Found &f)
+{
+    Decoded r;
+    const uint32_t k = (uint32_t)f.parts.size();
+    std::vector<uint64_t> raw(k);
+    const uint64_t src_len = f.src_len();
+    uint64_t total = 0;
+    int drc = 0;
+    if (f.by_index) {
+        // the index says what every block holds: one decode pass, every block bounded by its entry -- a block that decodes to more
+        // (NLZM_HIP_E_CAPACITY) or to less (NLZM_HIP_E_FORMAT) than that shows the index to be wrong, and the frame headers decide
+        // (the sizes are the index's word and nothing else yet: an index that asks for more memory than the host or the device has is a
+        //  wrong index, not a reason to die)
+        for (uint32_t i = 0; i < k; i++) total += f.ix.raw[i];
+        bool room = true;
+        try { r.out.resize((size_t)total); } catch (const std::exception &) { room = false; }
+        if (room && f.ix.typed()) drc = nlzm_hip_decompress_blocks_typed(f.parts[0].p, src_len, k, f.blen.data(), f.ix.raw.data(), f.ix.elem.data(), r.out.data(), total, raw.data(), &total);
+        else if (room) drc = nlzm_hip_decompress_blocks(f.parts[0].p, src_len, k, f.blen.data(), f.ix.raw.data(), r.out.data(), total, raw.data(), &total);
+        if (!room || drc == NLZM_HIP_E_CAPACITY || drc == NLZM_HIP_E_FORMAT || drc == NLZM_HIP_E_NOMEM) { r.index_wrong = true; drc = 0; std::vector<uint8_t>().swap(r.out); }
+    } else {
+        // no lengths anywhere in the format: a size pass, then the decode
+        drc = nlzm_hip_decompress_blocks(f.parts[0].p, src_len, k, f.blen.data(), nullptr, nullptr, 0, raw.data(), &total);
+        if (!drc) {
+            r.out.resize((size_t)total);
+            drc = nlzm_hip_decompress_blocks(f.parts[0].p, src_len, k, f.blen.data(), raw.data(), r.out.data(), total, nullptr, &total);
+        }
+    }
+    device_verdict(r, drc, f);
+    if (!r.failed && k > 1) printf("Blocks: %d\n", (int)k);
+    return r;
+}
+
+// without -gpu: a host thread per stream, the outputs in order; typed blocks' planes undone block by block, by the rule restated above
+Decoded decode_on_host(const Found &f)
+{
+    Decoded r;
+    const size_t k = f.parts.size();
+    std::vector<std::vector<uint8_t>> outs(k);
+    std::vector<int> rcs(k, 0);
+    std::vector<uint32_t> hbs(k, 0), fbs(k, 0);
+    if (f.ix.has_crc()) r.got_crcs.assign(k, 0);
+    for_each_block(k, [&](size_t i) {
+        rcs[i] = decode_stream(f.parts[i], outs[i], &hbs[i], &fbs[i]);
+        if (!rcs[i] && f.ix.has_crc()) r.got_crcs[i] = crc_calc(outs[i].data(), outs[i].size(), 0);
+    });
+    for (size_t i = 0; i < k && !r.rc; i++) {
+        r.rc = rcs[i];
+        if (!r.rc && f.by_index && outs[i].size() != f.ix.raw[i]) r.index_wrong = true;
+        if (k == 1) r.out.swap(outs[0]);            // (one stream, the reference's format: no copy of it)
+        else r.out.insert(r.out.end(), outs[i].begin(), outs[i].end());
+    }
+    r.hb = hbs[0]; r.fb = fbs[0];
+    if (k > 1 && !r.index_wrong) printf("Blocks: %d\n", (int)k);
+    if (f.ix.typed() && !r.rc && !r.index_wrong) {
+        std::vector<uint8_t> raw_bytes(r.out.size());
+        std::vector<uint64_t> at(k, 0);
+        for (size_t i = 1; i < k; i++) at[i] = at[i - 1] + f.ix.raw[i - 1];
+        for_each_block(k, [&](size_t i) { planes_undo(r.out.data() + at[i], raw_bytes.data() + at[i], f.ix.raw[i], f.ix.elem[i]); });
+        r.out.swap(raw_bytes);
+        r.got_crcs.clear();                         // (the CRC32s are the raw bytes': the caller hashes them)
+    }
+    return r;
+}
+
+int decode(const Options &o, bool to_file, const char *in_path, const char *out_path)
+{
+    if (to_file && refuse_existing(out_path)) return -1;
+    std::vector<uint8_t> in;
+    if (!slurp(in_path, in)) { printf("Error: %s file does not exist\n", in_path); return -1; }
+    OutFile fout;
+    if (to_file && !fout.open(out_path)) { printf("Error: %s file does not exist\n", out_path); return -1; }
     const clock_t t0 = clock();
-    if (on_gpu && nlzm_hip_init(0)) { printf("Error: %s\n", nlzm_hip_last_error()); fclose(fin); return -1; }
+    Index ix;
+    nlzm::index::parse((std::string(in_path) + ".idx").c_str(), ix);
+    if (ix.typed() && o.steps_k) { printf("Error: %s.idx is an NLZMIDX 3 index: -steps:K does not decode typed blocks (-elem:E)\n", in_path); return -1; }
+    if (o.on_gpu && nlzm_hip_init(0)) return hip_error();
+    Found f;
+    Decoded r;
+    // by the index first; an index that passes its checks and still does not describe these streams (stale, or of another file) is set aside,
+    // and the frame headers decide
+    for (int attempt = 0; attempt < 2; attempt++) {
+        f = find_parts(in, attempt == 0 ? &ix : nullptr, in_path);
+        if (ix.typed() && !f.by_index) {            // (only the index says which blocks are byte planes, and of which element size)
+            printf("Error: %s.idx (NLZMIDX 3) does not fit this file, and without it the byte planes of its blocks cannot be undone\n", in_path);
+            return -1;
+        }
+        r = Decoded{};
+        if (f.parts.empty()) r.rc = -3;
+        else if (o.on_gpu && o.steps_k) r = decode_in_steps(f, o.steps_k, fout.f);
+        else if (o.on_gpu && f.ix.has_crc() && !to_file && !f.ix.typed()) r = check_on_device(f);
+        else if (o.on_gpu) r = decode_on_device(f);
+        else r = decode_on_host(f);
+        if (r.failed) return -1;
+        if (!(f.by_index && (r.index_wrong || r.rc))) break;
+        printf("Note: %s.idx does not describe this file's blocks; they are found by their frame headers\n", in_path);
+    }
+    const size_t k = f.parts.size();
+    if (r.rc) { printf("Assert failed: malformed stream (%d)\n", r.rc); fout.done(); return -1; }      // (d leaves the file it opened, empty)
+    const bool check_crc = f.by_index && f.ix.has_crc();
+    if (check_crc && r.got_crcs.empty()) {
+        // one stream, typed blocks, or d -gpu: the bytes are on the host, hashed there block by block
+        r.got_crcs.assign(k, 0);
+        std::vector<uint64_t> at(k, 0);
+        for (size_t i = 1; i < k; i++) at[i] = at[i - 1] + f.ix.raw[i - 1];
+        for_each_block(k, [&](size_t i) { r.got_crcs[i] = crc_calc(r.out.data() + at[i], f.ix.raw[i], 0); });
+    }
+    uint32_t out_crc = 0;
+    if (r.out_on_device) for (size_t i = 0; i < k; i++) out_crc = nlzm_hip_crc32_combine(out_crc, r.got_crcs[i], f.ix.raw[i]);
+    else { out_crc = crc_calc(r.out.data(), r.out.size(), 0); r.out_size = r.out.size(); }
+    printf("Dictionary: %d KB\n", (int)(((1ull << r.hb) + 1023) >> 10));
+    printf("Frame: %d KB\n", (int)(((1u << r.fb) + 1023) >> 10));
+    if (to_file) { fwrite(r.out.data(), 1, r.out.size(), fout.f); fout.done(); }
+    printf("Working... %" PRIu64 " -> %" PRIu64 "\n", (uint64_t)in.size(), r.out_size);
+    printf("Done (output CRC32 %X, %.2f sec)\n", out_crc, (clock() - t0) / (double)CLOCKS_PER_SEC);
+    bool crc_bad = false;
+    if (check_crc) {
+        // the index's CRCs against what decoded: every block, then -- where the container is whole -- their combination against the file's
+        uint32_t comb = 0;
+        for (size_t i = 0; i < k; i++) comb = nlzm_hip_crc32_combine(comb, r.got_crcs[i], f.ix.raw[i]);
+        for (size_t i = 0; i < k && !crc_bad; i++)
+            if (r.got_crcs[i] != f.ix.crc[i]) { printf("CRC32 MISMATCH in block %zu (index says %08X, decoded %08X)\n", i + 1, f.ix.crc[i], r.got_crcs[i]); crc_bad = true; }
+        if (!crc_bad && !f.cut_tail && comb != f.ix.whole) { printf("CRC32 MISMATCH of the whole file (index says %08X, blocks combine to %08X)\n", f.ix.whole, comb); crc_bad = true; }
+        if (!crc_bad) printf("CRC32 ok (%zu blocks)\n", k);
+        else if (to_file) printf("Note: %s holds what decoded\n", out_path);
+    }
+    if (f.cut_tail) { printf("Error: the container is cut off inside block %zu (%zu bytes of it present); %zu complete blocks decoded\n", k + 1, f.cut_tail, k); return -2; }
+    return crc_bad ? -4 : 0;
+}
+
+// ---- x: byte ranges of what a container holds (not in the reference) -----------------------------------------------------------
+// The index as `x` needs it: the file itself is not consulted (it may be cut off behind the blocks a range needs), so the checks are structural.
+int extract(const char *in_path, const char *out_path, const std::vector<ByteRange> &ranges, bool on_gpu)
+{
+    if (refuse_existing(out_path)) return -1;
+    Index ix;
+    nlzm::index::parse((std::string(in_path) + ".idx").c_str(), ix);
+    if (ix.typed()) { printf("Error: %s.idx is an NLZMIDX 3 index: x does not read the ranges of typed blocks (-elem:E); d undoes their byte planes\n", in_path); return -1; }
+    std::unique_ptr<FILE, int (*)(FILE *)> fin(fopen(in_path, "rb"), fclose);
+    if (!fin) { printf("Error: %s file does not exist\n", in_path); return -1; }
+    fseeko(fin.get(), 0, SEEK_END);
+    const uint64_t file_size = (uint64_t)ftello(fin.get());
+    std::vector<uint8_t> whole_file;                // (without an index: the container is read whole and split by its frame headers)
+    const bool by_index = nlzm::index::structural(ix, kExtractTakes);
+    const clock_t t0 = clock();
+    if (on_gpu && nlzm_hip_init(0)) return hip_error();
     std::vector<std::vector<uint8_t>> decoded;      // host path: the needed blocks, whole
+    // `count` blocks decoded whole by the host decoder, one thread each: the i-th from its stream into decoded[slot(i)]
+    auto decode_blocks = [&](size_t count, auto stream, auto slot) {
+        std::vector<int> rcs(count, 0);
+        for_each_block(count, [&](size_t i) { uint32_t hb, fb; rcs[i] = decode_stream(stream(i), decoded[slot(i)], &hb, &fb); });
+        return rcs;
+    };
     if (!by_index) {
         printf("Note: no usable %s.idx; the blocks are found by their frame headers and sized by decoding them\n", in_path);
         ix = Index{};
         whole_file.resize((size_t)file_size);
-        fseeko(fin, 0, SEEK_SET);
-        if (file_size && fread(whole_file.data(), 1, (size_t)file_size, fin) != (size_t)file_size) { printf("Error: %s could not be read\n", in_path); fclose(fin); return -1; }
-        if (!nlzm_host::split_streams(Span{ whole_file.data(), whole_file.size() }, SIZE_MAX, ix.len)) { printf("Assert failed: malformed stream (-3)\n"); fclose(fin); return -1; }
+        fseeko(fin.get(), 0, SEEK_SET);
+        if (file_size && fread(whole_file.data(), 1, (size_t)file_size, fin.get()) != (size_t)file_size) { printf("Error: %s could not be read\n", in_path); return -1; }
+        if (!nlzm_host::split_streams(Span{ whole_file.data(), whole_file.size() }, SIZE_MAX, ix.len)) { printf("Assert failed: malformed stream (-3)\n"); return -1; }
         ix.off.assign(ix.len.size(), 0);
         for (size_t i = 1; i < ix.len.size(); i++) ix.off[i] = ix.off[i - 1] + ix.len[i - 1];
         ix.raw.assign(ix.off.size(), 0); ix.crc.assign(ix.off.size(), 0);
         if (on_gpu) {
             uint64_t total = 0;
-            if (nlzm_hip_decompress_blocks(whole_file.data(), ix.off.back() + ix.len.back(), (uint32_t)ix.off.size(), ix.len.data(), nullptr, nullptr, 0, ix.raw.data(), &total)) {
-                printf("Error: %s\n", nlzm_hip_last_error()); fclose(fin); return -1;
-            }
+            if (nlzm_hip_decompress_blocks(whole_file.data(), ix.off.back() + ix.len.back(), (uint32_t)ix.off.size(), ix.len.data(), nullptr, nullptr, 0, ix.raw.data(), &total)) return hip_error();
         } else {
             decoded.resize(ix.off.size());
-            std::vector<int> rcs(ix.off.size(), 0);
-            std::vector<std::thread> th;
-            for (size_t i = 0; i < ix.off.size(); i++)
-                th.emplace_back([&, i] { uint32_t hb, fb; rcs[i] = decode_stream(Span{ whole_file.data() + ix.off[i], (size_t)ix.len[i] }, decoded[i], &hb, &fb); });
-            for (auto &t : th) t.join();
+            const std::vector<int> rcs = decode_blocks(ix.off.size(), [&](size_t i) { return Span{ whole_file.data() + ix.off[i], (size_t)ix.len[i] }; }, [](size_t i) { return i; });
             for (size_t i = 0; i < ix.off.size(); i++) {
-                if (rcs[i]) { printf("Assert failed: malformed stream (%d)\n", rcs[i]); fclose(fin); return -1; }
+                if (rcs[i]) { printf("Assert failed: malformed stream (%d)\n", rcs[i]); return -1; }
                 ix.raw[i] = decoded[i].size();
             }
         }
@@ -164,7 +665,7 @@ int extract(const char *in_path, const char *out_path, const std::vector<ByteRan
     if (nlzm::range::make_plan(plan, (uint32_t)k, ix.raw.data(), (uint32_t)ranges.size(), off.data(), len.data(), ~0ull, nlzm::ErrText{ why, sizeof why })) {
         if (plan.bad_range < ranges.size()) printf("Error: range %" PRIu64 ":%" PRIu64 " runs over the %" PRIu64 " bytes the container holds\n", off[plan.bad_range], len[plan.bad_range], plan.total);
         else printf("Error: %s\n", why);
-        fclose(fin); return -1;
+        return -1;
     }
     const std::vector<uint64_t> &start = plan.start, &need = plan.need;
     const uint64_t out_size = plan.dst_len;
@@ -184,12 +685,12 @@ int extract(const char *in_path, const char *out_path, const std::vector<ByteRan
         for (size_t i = 0; i < picked.size(); i++) {
             const size_t b = picked[i];
             bool ok = ix.off[b] <= file_size && ix.len[b] <= file_size - ix.off[b];
-            if (ok && whole_file.empty()) ok = !fseeko(fin, (off_t)ix.off[b], SEEK_SET) && fread(packed.data() + sub_off[i], 1, (size_t)ix.len[b], fin) == (size_t)ix.len[b];
+            if (ok && whole_file.empty()) ok = !fseeko(fin.get(), (off_t)ix.off[b], SEEK_SET) && fread(packed.data() + sub_off[i], 1, (size_t)ix.len[b], fin.get()) == (size_t)ix.len[b];
             else if (ok) memcpy(packed.data() + sub_off[i], whole_file.data() + ix.off[b], (size_t)ix.len[b]);
-            if (!ok) { printf("Error: the container is cut off inside block %zu, which a range needs\n", b + 1); fclose(fin); return -1; }
+            if (!ok) { printf("Error: the container is cut off inside block %zu, which a range needs\n", b + 1); return -1; }
         }
     }
-    fclose(fin);
+    fin.reset();
     printf("Blocks: %zu, %zu of them read\n", k, picked.size());
     // a range lies in consecutive blocks, all of them picked but the empty ones: in the picked blocks' contents it starts at
     auto sub_of = [&](const ByteRange &r) {
@@ -202,7 +703,7 @@ int extract(const char *in_path, const char *out_path, const std::vector<ByteRan
     size_t full = 0;
     long bad_block = -1;
     uint32_t bad_got = 0;
-    const bool check_crc = by_index && ix.has_crc;
+    const bool check_crc = by_index && ix.has_crc();
     for (size_t i = 0; i < picked.size(); i++) full += need[picked[i]] == ix.raw[picked[i]];
     if (on_gpu) {
         for (size_t r = 0; r < ranges.size(); r++) off[r] = sub_of(ranges[r]);
@@ -211,8 +712,8 @@ int extract(const char *in_path, const char *out_path, const std::vector<ByteRan
         const int rc = picked.empty() ? 0
                      : nlzm_hip_read_ranges(packed.data(), packed_len, (uint32_t)picked.size(), sub_len.data(), sub_raw.data(), check_crc ? sub_crc.data() : nullptr,
                                             (uint32_t)ranges.size(), off.data(), len.data(), out.data(), out_size, &got, &first_bad);
-        if (rc == NLZM_HIP_E_FORMAT || rc == NLZM_HIP_E_CAPACITY) { printf("Error: a block does not decode to what its index entry says: %s\n", nlzm_hip_last_error()); return -1; }
-        if (rc) { printf("Error: %s\n", nlzm_hip_last_error()); return -1; }
+        if (rc == NLZM_HIP_E_FORMAT || rc == NLZM_HIP_E_CAPACITY) return hip_error("a block does not decode to what its index entry says: ");
+        if (rc) return hip_error();
         if (check_crc && first_bad < picked.size()) {
             // (what the block hashes to, for the message: decoded once more on the host, on this path only)
             std::vector<uint8_t> o; uint32_t hb, fb;
@@ -221,14 +722,10 @@ int extract(const char *in_path, const char *out_path, const std::vector<ByteRan
         }
         nlzm_hip_shutdown();
     } else {
-        // the needed blocks decoded whole by the host decoder, one thread per block, and sliced
+        // the needed blocks decoded whole and sliced
         if (decoded.empty()) {
             decoded.resize(k);
-            std::vector<int> rcs(picked.size(), 0);
-            std::vector<std::thread> th;
-            for (size_t i = 0; i < picked.size(); i++)
-                th.emplace_back([&, i] { uint32_t hb, fb; rcs[i] = decode_stream(Span{ packed.data() + sub_off[i], (size_t)sub_len[i] }, decoded[picked[i]], &hb, &fb); });
-            for (auto &t : th) t.join();
+            const std::vector<int> rcs = decode_blocks(picked.size(), [&](size_t i) { return Span{ packed.data() + sub_off[i], (size_t)sub_len[i] }; }, [&](size_t i) { return picked[i]; });
             for (size_t i = 0; i < picked.size(); i++) {
                 if (rcs[i]) { printf("Assert failed: malformed stream (%d)\n", rcs[i]); return -1; }
                 if (decoded[picked[i]].size() != ix.raw[picked[i]]) {
@@ -251,6 +748,7 @@ int extract(const char *in_path, const char *out_path, const std::vector<ByteRan
             if (c != ix.crc[b]) { bad_block = (long)b; bad_got = c; }
         }
     }
+    // (x opens its output when it has the bytes, and leaves it: what decoded is what a user can recover)
     FILE *fout = fopen(out_path, "wb");
     if (!fout) { printf("Error: %s file does not exist\n", out_path); return -1; }
     fwrite(out.data(), 1, out.size(), fout);
@@ -268,6 +766,83 @@ int extract(const char *in_path, const char *out_path, const std::vector<ByteRan
     return 0;
 }
 
+int hash(const char *in_path, bool on_gpu)
+{
+    std::vector<uint8_t> in;
+    if (!slurp(in_path, in)) { printf("Error: %s file does not exist\n", in_path); return -1; }
+    uint32_t crc = 0;
+    if (on_gpu) {
+        if (nlzm_hip_init(0) || nlzm_hip_crc32(in.data(), in.size(), 0, &crc)) return hip_error();
+        nlzm_hip_shutdown();
+    } else crc = crc_calc(in.data(), in.size(), 0);
+    printf("%X\n", crc);
+    return 0;
+}
+
+void usage()
+{
+    printf("Commands:\n"
+           "\t[flags] c [input] [output] - Compress input file to output file (best parser)\n"
+           "\td [input] [output] - Decompress input file to output file\n"
+           "\tt [input] - Decompress input file in memory\n"
+           "\th [input] - Calculate CRC32 for input file\n"
+           "\t-range:off:len [-range:...] x [input] [output] - (this build) write those byte ranges of what a block container holds; needs [input].idx\n"
+           "Flags:\n"
+           "\t-window:bits = Maximum window size in bits, default 22 (4 MB), min 15, max 28 (32 KB to 256 MB)\n"
+           "\t-blocks:k = (this build) compress k independent blocks, 1 to 65536: as many at once as a launch holds (64), more of them\n"
+           "\t            in sets one after another; d/t read the streams back to back\n"
+           "\t-cdc:B = (this build) c cuts the blocks by content on the GPU, 2^B bytes on average (B 10 to 30): an edit changes the blocks around it only\n"
+           "\t-elem:E = (this build) c compresses every block's byte planes at element size E (2, 4 or 8), alone or with -blocks:k / -cdc:B, and writes NLZMIDX 3; d / t undo them\n"
+           "\t-dedup = (this build) with -cdc:B: a block whose bytes an earlier block holds is not compressed again, its stream is a copy (the same container)\n"
+           "\t-gpus:g = (this build) the blocks on GPUs 0..g-1 of this node, -blocks:k of them on each (64 at most)\n"
+           "\t-verify = (this build) c decodes what it wrote on the GPU, one workgroup per stream, compares it with the input\n"
+           "\t          and removes the output if they differ\n"
+           "\t-gpu = (this build) d / t decode on the GPU, all blocks of a container at once (without it they run on the host); h hashes there\n"
+           "\t-steps:K = (this build) d -gpu / t -gpu decode in steps of K frames per block; d writes every step's bytes as they come\n"
+           "\t-crc = (this build) c hashes every block on the GPU and keeps the CRC32s in [output].idx (NLZMIDX 2), for one stream too;\n"
+           "\t       d / t compare what they decode with an index that holds CRC32s and exit with status -4 if a block differs\n");
+}
+
+// one flag, lower-cased and without its dashes, into the options; false: it is refused, and the message is printed
+bool parse_flag(const char *arg, Options &o)
+{
+    auto clamped = [](const char *digits, int lo, int hi) { const int v = atoi(digits); return (uint32_t)(v < lo ? lo : (v > hi ? hi : v)); };
+    unsigned long long v = 0, len = 0;
+    const char *p = nullptr;
+    if (!strncmp(arg, "window:", 7)) {
+        o.hist_bits = clamped(arg + 7, 15, 28);
+        printf("Window bits: %d\n", o.hist_bits);
+    } else if (!strncmp(arg, "blocks:", 7)) {
+        o.nblocks = clamped(arg + 7, 1, (int)nlzm::container::kMaxBlocks);
+        printf("Blocks: %d\n", o.nblocks);
+    } else if (!strncmp(arg, "gpus:", 5)) {
+        o.ngpus = clamped(arg + 5, 1, 64);
+        printf("GPUs: %d\n", o.ngpus);
+    } else if (!strncmp(arg, "cdc:", 4)) {
+        if (!parse_uint(p = arg + 4, 30, v) || *p || v < 10) { printf("Error: -cdc:B takes B from 10 to 30 (blocks of 2^B bytes on average)\n"); return false; }
+        o.cdc_bits = (uint32_t)v;
+    } else if (!strncmp(arg, "elem:", 5)) {
+        if (strcmp(arg + 5, "2") && strcmp(arg + 5, "4") && strcmp(arg + 5, "8")) { printf("Error: -elem:E takes E of 2, 4 or 8 (the bytes of an element)\n"); return false; }
+        o.elem = (uint32_t)(arg[5] - '0');
+    } else if (!strcmp(arg, "dedup")) {
+        o.dedup = true;
+    } else if (!strcmp(arg, "verify")) {
+        o.verify = true;
+    } else if (!strcmp(arg, "crc")) {
+        o.with_crc = true;
+    } else if (!strcmp(arg, "gpu")) {
+        o.on_gpu = true;
+    } else if (!strncmp(arg, "steps:", 6) && parse_uint(p = arg + 6, 0xFFFFFFFFull, v) && !*p && v >= 1) {          // 1 .. 2^32 - 1
+        o.steps_k = (uint32_t)v;
+    } else if (!strncmp(arg, "range:", 6) && parse_uint(p = arg + 6, ~0ull, v) && *p++ == ':' && parse_uint(p, ~0ull, len) && !*p) {
+        o.ranges.push_back(ByteRange{ v, len });
+    } else {
+        printf("Unrecognized flag %s\n", arg);
+        return false;
+    }
+    return true;
+}
+
 }  // namespace
 
 int main(int argc, char **argv)
@@ -277,577 +852,30 @@ int main(int argc, char **argv)
     //  the variable at the first HIP call -- nlzm_hip_init sets it too, this is for a main that touches HIP before it)
     setenv("GPU_MAX_HW_QUEUES", "16", 0);
     crc_init();
-    uint32_t hist_bits = 22;                                                      // :2071
-    uint32_t nblocks = 1;                           // -blocks:k (not in the reference): k independent streams, back to back
-    uint32_t ngpus = 0;                             // -gpus:g (not in the reference): the blocks on g GPUs of this node, -blocks:k on each
-    bool verify = false;                            // -verify (not in the reference): c decodes what it wrote on the device and compares it with the input
-    bool with_crc = false;                          // -crc (not in the reference): c keeps every block's CRC32, hashed on the device, in the index (NLZMIDX 2); d / t check them
-    bool on_gpu = false;                            // -gpu (not in the reference): d / t decode on the device; without it they are host-only and need none
-    uint32_t cdc_bits = 0;                          // -cdc:B (not in the reference): c cuts the blocks by content on the device, 2^B bytes a block on average
-    bool dedup = false;                             // -dedup (not in the reference): with -cdc:B, c does not compress a block again whose bytes an earlier block holds
-    uint32_t elem = 0;                              // -elem:E (not in the reference): c compresses every block's byte planes at element size E (NLZMIDX 3); d / t undo them
-    uint32_t steps_k = 0;                           // -steps:K (not in the reference): d -gpu / t -gpu decode in steps of K frames per block
-    std::vector<ByteRange> ranges;                  // -range:off:len (not in the reference): what x writes, in this order
+    Options o;
     while (argc >= 2 && *argv[1] == '-') {
         char *arg = argv[1];
         argv++; argc--;
         lower(arg);
         while (*arg == '-') ++arg;
-        if (!strncmp(arg, "window:", 7)) {
-            const int v = atoi(arg + 7);
-            hist_bits = (uint32_t)(v < 15 ? 15 : (v > 28 ? 28 : v));
-            printf("Window bits: %d\n", hist_bits);
-        } else if (!strncmp(arg, "blocks:", 7)) {
-            const int v = atoi(arg + 7);
-            nblocks = (uint32_t)(v < 1 ? 1 : (v > (int)nlzm::container::kMaxBlocks ? (int)nlzm::container::kMaxBlocks : v));
-            printf("Blocks: %d\n", nblocks);
-        } else if (!strncmp(arg, "gpus:", 5)) {
-            const int v = atoi(arg + 5);
-            ngpus = (uint32_t)(v < 1 ? 1 : (v > 64 ? 64 : v));
-            printf("GPUs: %d\n", ngpus);
-        } else if (!strncmp(arg, "cdc:", 4)) {
-            // digits and nothing else, 10 .. 30
-            unsigned v = 0;
-            const char *p = arg + 4;
-            bool ok = *p >= '0' && *p <= '9';
-            for (; ok && *p >= '0' && *p <= '9'; p++) { v = v * 10 + (unsigned)(*p - '0'); if (v > 30) ok = false; }
-            if (!ok || *p || v < 10) { printf("Error: -cdc:B takes B from 10 to 30 (blocks of 2^B bytes on average)\n"); return -1; }
-            cdc_bits = v;
-        } else if (!strncmp(arg, "elem:", 5)) {
-            if (strcmp(arg + 5, "2") && strcmp(arg + 5, "4") && strcmp(arg + 5, "8")) { printf("Error: -elem:E takes E of 2, 4 or 8 (the bytes of an element)\n"); return -1; }
-            elem = (uint32_t)(arg[5] - '0');
-        } else if (!strcmp(arg, "dedup")) {
-            dedup = true;
-        } else if (!strcmp(arg, "verify")) {
-            verify = true;
-        } else if (!strcmp(arg, "crc")) {
-            with_crc = true;
-        } else if (!strcmp(arg, "gpu")) {
-            on_gpu = true;
-        } else if (!strncmp(arg, "steps:", 6)) {
-            // digits and nothing else, 1 .. 2^32 - 1 (as strict as -range:)
-            unsigned long long v = 0;
-            const char *p = arg + 6;
-            bool ok = *p >= '0' && *p <= '9';
-            for (; ok && *p >= '0' && *p <= '9'; p++) { v = v * 10 + (unsigned long long)(*p - '0'); if (v > 0xFFFFFFFFull) ok = false; }
-            if (!ok || *p || v < 1) { printf("Unrecognized flag %s\n", arg); return -1; }
-            steps_k = (uint32_t)v;
-        } else if (!strncmp(arg, "range:", 6)) {
-            // digits ':' digits and nothing else; a number that does not fit 64 bits is refused, not saturated
-            auto number = [](const char *&p, unsigned long long &v) {
-                if (*p < '0' || *p > '9') return false;
-                for (v = 0; *p >= '0' && *p <= '9'; p++) {
-                    if (v > (~0ull - (unsigned long long)(*p - '0')) / 10) return false;
-                    v = v * 10 + (unsigned long long)(*p - '0');
-                }
-                return true;
-            };
-            const char *p = arg + 6;
-            unsigned long long off = 0, len = 0;
-            if (!number(p, off) || *p++ != ':' || !number(p, len) || *p) { printf("Unrecognized flag %s\n", arg); return -1; }
-            ranges.push_back(ByteRange{ off, len });
-        } else {
-            printf("Unrecognized flag %s\n", arg);
-            return -1;
-        }
+        if (!parse_flag(arg, o)) return -1;
     }
     const int cmd = argc >= 2 ? (argv[1][0] | 0x20) : 0;
-    if (cdc_bits && (nblocks > 1 || ngpus)) { printf("Error: -cdc:B cuts the blocks by content; it does not go together with -blocks:k or -gpus:g\n"); return -1; }
-    if (dedup && !cdc_bits) { printf("Error: -dedup skips the duplicates among the blocks that -cdc:B cuts; it needs -cdc:B\n"); return -1; }
-    if (elem && ngpus) { printf("Error: -elem:E filters the blocks of one GPU's container; it does not go together with -gpus:g\n"); return -1; }
-    if (elem) with_crc = true;                      // (the index holds the CRC32s of the RAW bytes: what d / t hold the undone planes against)
-    if (ngpus && nblocks > 64) { nblocks = 64; printf("Blocks: %d (on each GPU: a launch holds no more)\n", nblocks); }
-    if (steps_k && !(on_gpu && ((argc == 4 && cmd == 'd') || (argc == 3 && cmd == 't')))) { printf("Error: -steps:K is for d -gpu and t -gpu\n"); return -1; }
+    if (o.cdc_bits && (o.nblocks > 1 || o.ngpus)) { printf("Error: -cdc:B cuts the blocks by content; it does not go together with -blocks:k or -gpus:g\n"); return -1; }
+    if (o.dedup && !o.cdc_bits) { printf("Error: -dedup skips the duplicates among the blocks that -cdc:B cuts; it needs -cdc:B\n"); return -1; }
+    if (o.elem && o.ngpus) { printf("Error: -elem:E filters the blocks of one GPU's container; it does not go together with -gpus:g\n"); return -1; }
+    if (o.elem) o.with_crc = true;                  // (the index holds the CRC32s of the RAW bytes: what d / t hold the undone planes against)
+    if (o.ngpus && o.nblocks > 64) { o.nblocks = 64; printf("Blocks: %d (on each GPU: a launch holds no more)\n", o.nblocks); }
+    const bool decodes = (argc == 4 && cmd == 'd') || (argc == 3 && cmd == 't');
+    if (o.steps_k && !(o.on_gpu && decodes)) { printf("Error: -steps:K is for d -gpu and t -gpu\n"); return -1; }
     if (argc == 4 && cmd == 'c') {
-        if (FILE *probe = fopen(argv[3], "rb")) { printf("Error: %s already exists\n", argv[3]); fclose(probe); return -1; }
-        const bool one_stream = !ngpus && nblocks == 1 && !verify && !cdc_bits && !elem;      // (-verify, -cdc and -elem need the input whole: the one-call path)
-        std::vector<uint8_t> in;
-        FILE *fin = nullptr;
-        uint64_t in_size = 0;
-        if (one_stream) {       // read, uploaded and compressed piece by piece (nlzm_hip_feed_*): the file is never whole in host memory
-            fin = fopen(argv[2], "rb");
-            if (!fin) { printf("Error: %s file does not exist\n", argv[2]); return -1; }
-            fseeko(fin, 0, SEEK_END);
-            in_size = (uint64_t)ftello(fin);
-            fseeko(fin, 0, SEEK_SET);
-        } else {
-            if (!slurp(argv[2], in)) { printf("Error: %s file does not exist\n", argv[2]); return -1; }
-            in_size = in.size();
-        }
-        FILE *fout = fopen(argv[3], "wb");
-        if (!fout) { printf("Error: %s file does not exist\n", argv[3]); if (fin) fclose(fin); return -1; }
-        if (!ngpus && nlzm_hip_init(0)) { printf("Error: %s\n", nlzm_hip_last_error()); fclose(fout); remove(argv[3]); return -1; }
-        uint32_t nstreams = ngpus ? ngpus * nblocks : nblocks;
-        std::vector<uint64_t> boff, braw;           // every block's bytes of the input: cut by content, or the equal partition
-        if (cdc_bits) {
-            // the cut points from the device, with the default lengths: 2^(B - 2) .. 2^(B + 2) bytes a block (2^31 at most)
-            const uint64_t min_len = 1ull << (cdc_bits - 2), max_len = cdc_bits + 2 > 31 ? 1ull << 31 : 1ull << (cdc_bits + 2);
-            std::vector<uint64_t> cuts(nlzm::container::kMaxBlocks - 1);
-            uint32_t ncuts = 0;
-            const int crc = nlzm_hip_cut_points(in.data(), in.size(), cdc_bits, min_len, max_len, cuts.data(), (uint32_t)cuts.size(), &ncuts);
-            if (crc == NLZM_HIP_E_CAPACITY) printf("Error: -cdc:%u cuts this input into %" PRIu64 " blocks, a container holds %u at most: raise B\n", cdc_bits, (uint64_t)ncuts + 1, nlzm::container::kMaxBlocks);
-            else if (crc) printf("Error: %s\n", nlzm_hip_last_error());
-            if (crc) { fclose(fout); remove(argv[3]); return -1; }
-            if (elem) {                                 // (whole elements a block: the cuts rounded down, equal ones dropped)
-                uint32_t kept = 0;
-                for (uint32_t i = 0; i < ncuts; i++) {
-                    const uint64_t c = cuts[i] / elem * elem;
-                    if (c && (!kept || c > cuts[kept - 1])) cuts[kept++] = c;
-                }
-                ncuts = kept;
-            }
-            nstreams = ncuts + 1;
-            for (uint32_t i = 0; i < nstreams; i++) {
-                const uint64_t lo = i ? cuts[i - 1] : 0, hi = i < ncuts ? cuts[i] : (uint64_t)in.size();
-                boff.push_back(lo); braw.push_back(hi - lo);
-            }
-            printf("Blocks: %u (cut by content)\n", nstreams);
-        } else if (!one_stream) {
-            uint64_t per = (in.size() + nstreams - 1) / nstreams;
-            if (elem) per = (per + elem - 1) / elem * elem;      // (whole elements a block)
-            for (uint32_t i = 0; i < nstreams; i++) {
-                const uint64_t lo = (uint64_t)i * per < in.size() ? (uint64_t)i * per : in.size(), hi = lo + per < in.size() ? lo + per : in.size();
-                boff.push_back(lo); braw.push_back(hi - lo);
-            }
-        }
-        uint32_t hb, fb, cs, feed;
-        nlzm_hip_geometry(in_size, hist_bits, &hb, &fb, &cs, &feed);
-        {   // the reference's summary (:1755-1759): sizes of its own structures for this window
-            const uint32_t c1 = hb < 15 ? 15 : (hb > 17 ? 17 : hb), c2 = hb < 16 ? 16 : (hb > 20 ? 20 : hb), c3 = hb < 16 ? 16 : (hb > 22 ? 22 : hb);
-            const uint64_t mf = (4ull << 12) + (8ull << (12 + c1 - 15)) + (4ull << (13 + c2 - 16)) + (8ull << hb) + (4ull << (15 + c3 - 16));
-            printf("Model: %d KB\n", 2);
-            printf("Parser: %d KB\n", 65);
-            printf("Dictionary: %d KB\n", (int)(((1ull << hb) + 1023) >> 10));
-            printf("Frame: %d KB\n", (int)(((1u << fb) + 1023) >> 10));
-            printf("Dictionary search: %d KB\n", (int)((mf + 1023) >> 10));
-        }
-        if (nstreams > 1)
-            printf("Note: %u independent streams are written back to back; this program's d/t read them, the reference's d "
-                   "stops after the first\n", nstreams);
-        printf("Working...\r");
-        uint64_t out_n = 0;
-        const clock_t t0 = clock();
-        struct timespec w0, w1;
-        clock_gettime(CLOCK_MONOTONIC, &w0);
-        if (one_stream) {
-            // the reference's loop in big steps: read a piece, hand it over, write the frames that are finished (:1774-1778, :1853, :1870-1885)
-            std::vector<uint8_t> piece(16u << 20), obuf(16u << 20);
-            uint32_t crc = 0;
-            int rc = nlzm_hip_feed_begin(in_size, hist_bits);
-            auto drain = [&]() {
-                for (uint64_t got = 1; !rc && got;) {
-                    rc = nlzm_hip_feed_output(obuf.data(), obuf.size(), &got);
-                    if (!rc && got) { fwrite(obuf.data(), 1, (size_t)got, fout); out_n += got; }
-                }
-            };
-            for (uint64_t done = 0; !rc && done < in_size;) {
-                const size_t m = (size_t)(in_size - done < piece.size() ? in_size - done : piece.size());
-                if (fread(piece.data(), 1, m, fin) != m) { printf("Error: %s could not be read\n", argv[2]); rc = -1; break; }
-                if (!with_crc) crc = crc_calc(piece.data(), m, crc);
-                rc = nlzm_hip_feed(piece.data(), m);
-                done += m;
-                drain();
-                printf("Working... %" PRIu64 " -> %" PRIu64 "\r", done, out_n);
-                fflush(stdout);
-            }
-            if (!rc) rc = nlzm_hip_feed_finish();
-            drain();
-            if (!rc && with_crc) rc = nlzm_hip_feed_input_crc32(&crc);      // (the input is whole in HBM and nowhere on the host: hashed where it lies)
-            nlzm_hip_feed_end();
-            fclose(fin);
-            clock_gettime(CLOCK_MONOTONIC, &w1);
-            if (rc) { if (rc != -1) printf("Error: %s\n", nlzm_hip_last_error()); fclose(fout); remove(argv[3]); return -1; }
-            fclose(fout);
-            if (with_crc) {
-                const std::string ip = std::string(argv[3]) + ".idx";
-                if (FILE *fi = fopen(ip.c_str(), "wb")) {
-                    fprintf(fi, "NLZMIDX 2 1 %" PRIu64 " %" PRIu64 " %08X\n0 %" PRIu64 " %" PRIu64 " %08X\n", in_size, out_n, crc, out_n, in_size, crc);
-                    fclose(fi);
-                    printf("Block index: %s\n", ip.c_str());
-                }
-            }
-            printf("Working... %" PRIu64 " -> %" PRIu64 "\n", in_size, out_n);
-            printf("Done (input CRC32 %X, %.2f sec)\n", crc, (double)(w1.tv_sec - w0.tv_sec) + 1e-9 * (double)(w1.tv_nsec - w0.tv_nsec));
-            nlzm_hip_shutdown();
-            return 0;
-        }
-        // room for the streams (a guaranteed bound: 9.7 GB at 65,536 blocks).  Not a vector: nothing is filled, and the pages behind the streams' end are never touched
-        const size_t out_room = ngpus ? (size_t)nlzm_hip_compress_bound(in.size()) + (size_t)nstreams * (16 + 131072)
-                              : cdc_bits || elem ? (size_t)nlzm_hip_compress_ranges_bound(nstreams, braw.data()) : (size_t)nlzm_hip_compress_blocks_bound(in.size(), nblocks);
-        struct Room { uint8_t *p; size_t n; uint8_t *data() const { return p; } size_t size() const { return n; } ~Room() { free(p); } } out{ (uint8_t *)malloc(out_room ? out_room : 1), out_room };
-        if (!out.data()) { printf("Error: no memory for %zu bytes of output\n", out_room); fclose(fout); remove(argv[3]); return -1; }
-        std::vector<uint64_t> blen(nstreams);
-        std::vector<int> devs;
-        for (uint32_t d = 0; d < ngpus; d++) devs.push_back((int)d);
-        if (dedup && nlzm_hip_set_option("dedup_ranges", 1)) { printf("Error: %s\n", nlzm_hip_last_error()); fclose(fout); remove(argv[3]); return -1; }
-        const std::vector<uint8_t> elems(nstreams, (uint8_t)elem);
-        const int rc = elem ? nlzm_hip_compress_ranges_typed(in.data(), in.size(), nstreams, boff.data(), braw.data(), elems.data(), hist_bits, out.data(), out.size(), blen.data(), &out_n)
-                     : cdc_bits ? nlzm_hip_compress_ranges(in.data(), in.size(), nstreams, boff.data(), braw.data(), hist_bits, out.data(), out.size(), blen.data(), &out_n)
-                     : ngpus ? nlzm_hip_compress_blocks_multi(devs.data(), ngpus, nblocks, in.data(), in.size(), hist_bits, out.data(), out.size(), blen.data(), &out_n)
-                     : nblocks > 1 ? nlzm_hip_compress_blocks(in.data(), in.size(), nblocks, hist_bits, out.data(), out.size(), blen.data(), &out_n)
-                                   : nlzm_hip_compress(in.data(), in.size(), hist_bits, out.data(), out.size(), &out_n);
-        clock_gettime(CLOCK_MONOTONIC, &w1);
-        (void)t0;
-        if (rc) { printf("Error: %s\n", nlzm_hip_last_error()); fclose(fout); remove(argv[3]); return -1; }
-        if (nstreams == 1) blen[0] = out_n;
-        if (dedup) {        // (the finder's counters of the call: the blocks that were another's copy, and their bytes)
-            uint64_t distinct = nstreams, dup_bytes = 0;
-            (void)nlzm_hip_get_counter("dedup_distinct", &distinct);
-            (void)nlzm_hip_get_counter("dedup_dup_bytes", &dup_bytes);
-            printf("Duplicates: %" PRIu64 " of %u blocks (%" PRIu64 " bytes) not compressed again\n", (uint64_t)nstreams - distinct, nstreams, dup_bytes);
-        }
-        if (verify) {
-            // the stream(s) decoded on the device, one workgroup each, and compared there with the input; neither comes back to the host
-            uint64_t first = 0, decoded = 0;
-            struct timespec v0, v1;
-            clock_gettime(CLOCK_MONOTONIC, &v0);
-            int vrc = ngpus ? nlzm_hip_init(0) : 0;
-            if (!vrc && elem) {
-                // typed blocks: decoded through the typed entry point, which undoes the planes, and compared here (the blocks are the input, in order)
-                std::vector<uint8_t> back(in.size());
-                vrc = nlzm_hip_decompress_blocks_typed(out.data(), out_n, nstreams, blen.data(), braw.data(), elems.data(), back.data(), back.size(), nullptr, &decoded);
-                for (first = 0; !vrc && first < decoded && first < in.size() && back[first] == in[first];) first++;
-            } else
-            if (!vrc) vrc = nlzm_hip_verify(out.data(), out_n, nstreams, nstreams > 1 ? blen.data() : nullptr, in.data(), in.size(), &first, &decoded);
-            clock_gettime(CLOCK_MONOTONIC, &v1);
-            if (vrc) { printf("Error: verify: %s\n", nlzm_hip_last_error()); fclose(fout); remove(argv[3]); return -1; }
-            if (!NLZM_HIP_VERIFY_EQUAL(first, decoded, (uint64_t)in.size())) {
-                if (first < in.size() && first < decoded) printf("Verify FAILED: the stream decodes to something else from offset %" PRIu64 "; %s removed\n", first, argv[3]);
-                else printf("Verify FAILED: the stream decodes to %" PRIu64 " bytes, the input has %" PRIu64 " (equal up to offset %" PRIu64 "); %s removed\n", decoded, (uint64_t)in.size(), first, argv[3]);
-                fclose(fout); remove(argv[3]);
-                return -3;
-            }
-            uint64_t dev_us = 0;
-            (void)nlzm_hip_get_counter("decode_us", &dev_us);
-            printf("Verified (%.2f sec, %.2f of them decoding on the device)\n", (double)(v1.tv_sec - v0.tv_sec) + 1e-9 * (double)(v1.tv_nsec - v0.tv_nsec), 1e-6 * (double)dev_us);
-        }
-        // -crc: every block's CRC32 from the device, on a re-upload of the input as -verify makes one; the whole file's is their combination
-        std::vector<uint32_t> bcrc(nstreams, 0);
-        uint32_t whole = 0;
-        if (with_crc) {
-            int crc_rc = ngpus ? nlzm_hip_init(0) : 0;
-            if (!crc_rc) crc_rc = nlzm_hip_crc32_ranges(in.data(), in.size(), nstreams, boff.data(), braw.data(), bcrc.data());
-            if (crc_rc) { printf("Error: crc: %s\n", nlzm_hip_last_error()); fclose(fout); remove(argv[3]); return -1; }
-            for (uint32_t i = 0; i < nstreams; i++) whole = nlzm_hip_crc32_combine(whole, bcrc[i], braw[i]);
-        }
-        fwrite(out.data(), 1, (size_t)out_n, fout);
-        fclose(fout);
-        if (nstreams > 1 || with_crc || cdc_bits || elem) {
-            // the block index, a sidecar: where every block's stream starts, how long it is and how many input bytes it holds.  The
-            // streams stay self-delimiting -- the index only saves d/t the hop over every frame header of every block before the parallel decode can
-            // start, and keeps the later blocks' boundaries when the container is damaged inside an earlier one.
-            const std::string ip = std::string(argv[3]) + ".idx";
-            if (FILE *fi = fopen(ip.c_str(), "wb")) {
-                if (elem) fprintf(fi, "NLZMIDX 3 %u %" PRIu64 " %" PRIu64 " %08X\n", nstreams, (uint64_t)in.size(), out_n, whole);
-                else if (with_crc) fprintf(fi, "NLZMIDX 2 %u %" PRIu64 " %" PRIu64 " %08X\n", nstreams, (uint64_t)in.size(), out_n, whole);
-                else fprintf(fi, "NLZMIDX 1 %u %" PRIu64 " %" PRIu64 "\n", nstreams, (uint64_t)in.size(), out_n);
-                uint64_t off = 0;
-                for (uint32_t i = 0; i < nstreams; i++) {       // (each block's raw length its true one: the equal partition's, or the content's)
-                    if (elem) fprintf(fi, "%" PRIu64 " %" PRIu64 " %" PRIu64 " %08X %u\n", off, blen[i], braw[i], bcrc[i], elem);
-                    else if (with_crc) fprintf(fi, "%" PRIu64 " %" PRIu64 " %" PRIu64 " %08X\n", off, blen[i], braw[i], bcrc[i]);
-                    else fprintf(fi, "%" PRIu64 " %" PRIu64 " %" PRIu64 "\n", off, blen[i], braw[i]);
-                    off += blen[i];
-                }
-                fclose(fi);
-                printf("Block index: %s\n", ip.c_str());
-            }
-        }
-        printf("Working... %" PRIu64 " -> %" PRIu64 "\n", (uint64_t)in.size(), out_n);
-        printf("Done (input CRC32 %X, %.2f sec)\n", with_crc ? whole : crc_calc(in.data(), in.size(), 0),
-               (double)(w1.tv_sec - w0.tv_sec) + 1e-9 * (double)(w1.tv_nsec - w0.tv_nsec));
-        nlzm_hip_shutdown();
-    } else if ((argc == 4 && cmd == 'd') || (argc == 3 && cmd == 't')) {
-        if (cmd == 'd') {
-            if (FILE *probe = fopen(argv[3], "rb")) { printf("Error: %s already exists\n", argv[3]); fclose(probe); return -1; }
-        }
-        std::vector<uint8_t> in, out;
-        if (!slurp(argv[2], in)) { printf("Error: %s file does not exist\n", argv[2]); return -1; }
-        FILE *fout = nullptr;
-        if (cmd == 'd') {
-            fout = fopen(argv[3], "wb");
-            if (!fout) { printf("Error: %s file does not exist\n", argv[3]); return -1; }
-        }
-        uint32_t hb = 0, fb = 0;
-        const clock_t t0 = clock();
-        // one stream (the reference's format), or several back to back (block mode): found by hopping over the frames,
-        // decoded on a host thread each, written in order
-        std::vector<Span> parts;
-        std::vector<uint64_t> raws;                 // (by index) the input bytes every block holds
-        std::vector<uint8_t> idx_elems;             // (by a version-3 index) every block's element size: its bytes are byte planes
-        std::vector<uint32_t> idx_crcs;             // (by a version-2 or -3 index) every block's CRC32, and the whole file's
-        uint32_t idx_whole = 0;
-        bool idx_has_crc = false;
-        size_t cut_tail = 0;
-        bool by_index = false;
-        auto find_parts = [&](bool use_index) {
-            parts.clear(); raws.clear(); idx_crcs.clear(); idx_elems.clear(); cut_tail = 0; by_index = false; idx_has_crc = false;
-            // the sidecar index of a block container, if it is there and fits the file: the blocks' boundaries without hopping over their frames
-            const std::string ip = std::string(argv[2]) + ".idx";
-            FILE *fi = use_index ? fopen(ip.c_str(), "rb") : nullptr;
-            if (fi) {
-                unsigned ver = 0, k = 0;
-                unsigned long long n_in = 0, n_out = 0;
-                std::vector<Span> idx;
-                std::vector<uint64_t> idx_raw;
-                std::vector<uint32_t> idx_crc;
-                std::vector<uint8_t> idx_elem;
-                unsigned whole = 0;
-                bool ok = fscanf(fi, "NLZMIDX %u %u %llu %llu", &ver, &k, &n_in, &n_out) == 4 && (ver >= 1 && ver <= 3) && k >= 1 && k <= 4096 && n_out >= in.size();
-                if (ok && ver >= 2) ok = fscanf(fi, "%x", &whole) == 1;         // (version 2: version 1 and a CRC32 behind the header's and every block's fields)
-                unsigned long long expect = 0, raw_sum = 0;
-                bool cut = false;
-                for (unsigned i = 0; ok && i < k && !cut; i++) {
-                    unsigned long long off = 0, len = 0, raw = 0;
-                    unsigned bc = 0, be = 1;
-                    ok = fscanf(fi, "%llu %llu %llu", &off, &len, &raw) == 3 && (ver == 1 || fscanf(fi, "%x", &bc) == 1) && (ver < 3 || (fscanf(fi, "%u", &be) == 1 && (be == 1 || be == 2 || be == 4 || be == 8))) &&
-                         off == expect && len >= 8 && off <= in.size() && raw <= n_in - raw_sum;
-                    if (ok && len > in.size() - off) { cut = true; break; }      // (the file ends inside this block: the ones in front of it are whole; no off + len, which can wrap)
-                    // (a block's stream starts with its header and ends with its terminator, :1915-1921, :646-648)
-                    if (ok) ok = in[off] == 0 && in[off + 1] >= 10 && in[off + 1] <= 28 && be32(&in[off + len - 4]) == 0;
-                    if (ok) { idx.push_back(Span{ in.data() + off, (size_t)len }); idx_raw.push_back(raw); idx_crc.push_back(bc); idx_elem.push_back((uint8_t)be); expect = off + len; raw_sum += raw; }
-                }
-                fclose(fi);
-                if (ok && !idx.empty() && (cut || (expect == in.size() && n_out == in.size() && raw_sum == n_in))) {
-                    parts = idx; raws = idx_raw; by_index = true;
-                    if (ver >= 2) { idx_crcs = idx_crc; idx_whole = whole; idx_has_crc = true; }
-                    if (ver == 3) idx_elems = idx_elem;
-                    if (cut) cut_tail = in.size() - (size_t)expect;
-                } else printf("Note: %s does not fit this file; the blocks are found by their frame headers\n", ip.c_str());
-            }
-            for (size_t pos = 0; !by_index && pos < in.size();) {
-                const Span rest{ in.data() + pos, in.size() - pos };
-                const size_t len = stream_length(rest);
-                if (!len) {
-                    // what follows is not a stream: the reference stops at the first terminator (:646-648) and so do we;
-                    // a container that is cut off inside its first stream is malformed
-                    if (parts.empty()) break;
-                    // a further stream header (:1915-1921: hist_bits, frame_bits, both big-endian 16-bit) with a frame that is cut off:
-                    // the complete streams are decoded and written, and the exit status says that the container was cut
-                    const bool header = rest.n >= 4 && rest.p[0] == 0 && rest.p[1] >= 10 && rest.p[1] <= 28 && rest.p[2] == 0 && rest.p[3] >= 12 && rest.p[3] <= 20;
-                    if (header) cut_tail = rest.n;
-                    else printf("Note: %zu bytes after the last stream ignored\n", rest.n);
-                    break;
-                }
-                parts.push_back(Span{ rest.p, len });
-                pos += len;
-            }
-        };
-        const bool typed_idx = typed_index(std::string(argv[2]) + ".idx");
-        if (typed_idx && steps_k) { printf("Error: %s.idx is an NLZMIDX 3 index: -steps:K does not decode typed blocks (-elem:E)\n", argv[2]); if (fout) { fclose(fout); remove(argv[3]); } return -1; }
-        if (on_gpu && nlzm_hip_init(0)) { printf("Error: %s\n", nlzm_hip_last_error()); if (fout) { fclose(fout); remove(argv[3]); } return -1; }
-        int rc = 0;
-        std::vector<uint32_t> got_crcs;             // what the blocks decoded to hash to (where a version-2 index gives CRCs to hold against)
-        uint64_t out_size = 0;
-        bool out_on_device = false;                 // t -gpu with a version-2 index: decoded and hashed on the device, nothing came back
-        for (int attempt = 0; attempt < 2; attempt++) {
-            find_parts(attempt == 0);
-            if (typed_idx && !by_index) {           // (only the index says which blocks are byte planes, and of which element size)
-                printf("Error: %s.idx (NLZMIDX 3) does not fit this file, and without it the byte planes of its blocks cannot be undone\n", argv[2]);
-                if (fout) { fclose(fout); remove(argv[3]); }
-                return -1;
-            }
-            const bool typed = !idx_elems.empty();
-            out.clear(); got_crcs.clear(); out_on_device = false; out_size = 0;
-            rc = parts.empty() ? -3 : 0;
-            bool index_wrong = false;               // a block did not decode to the bytes its index entry says it holds
-            if (!rc && on_gpu && steps_k) {
-                // the same decode in steps of K frames per block (nlzm_hip_decode_*): after every step each block's new bytes are fetched, hashed and --
-                // d -- written at the block's offset, so the host holds one step's output at a time
-                const uint32_t k = (uint32_t)parts.size();
-                std::vector<uint64_t> blen(k), raw(k), at(k, 0), done(k, 0), had(k, 0);
-                for (uint32_t i = 0; i < k; i++) blen[i] = parts[i].n;
-                const uint64_t src_len = (uint64_t)(parts.back().p + parts.back().n - parts[0].p);
-                uint64_t total = 0, launches = 0;
-                int drc = 0;
-                if (by_index) raw = raws;
-                else drc = nlzm_hip_decompress_blocks(parts[0].p, src_len, k, blen.data(), nullptr, nullptr, 0, raw.data(), &total);      // (no lengths anywhere in the format: a size pass)
-                for (uint32_t i = 1; i < k; i++) at[i] = at[i - 1] + raw[i - 1];
-                if (!drc) drc = nlzm_hip_decode_begin(parts[0].p, src_len, k, blen.data(), raw.data(), 0);
-                std::vector<uint32_t> crcs(k, 0);
-                std::vector<uint8_t> piece;
-                int finished = 0;
-                bool open = !drc;
-                while (!drc && !finished) {
-                    drc = nlzm_hip_decode_step(steps_k, nullptr, done.data(), &finished, nullptr);
-                    if (drc) { open = false; break; }           // (a failing step has closed the set)
-                    for (uint32_t i = 0; i < k && !drc; i++) {
-                        const uint64_t n = done[i] - had[i];
-                        if (!n) continue;
-                        piece.resize((size_t)n);
-                        drc = nlzm_hip_decode_fetch(at[i] + had[i], n, piece.data());
-                        if (drc) break;
-                        crcs[i] = crc_calc(piece.data(), n, crcs[i]);
-                        if (fout) { fseeko(fout, (off_t)(at[i] + had[i]), SEEK_SET); fwrite(piece.data(), 1, (size_t)n, fout); }
-                        had[i] = done[i];
-                    }
-                }
-                if (!drc) { (void)nlzm_hip_get_counter("decode_steps", &launches); drc = nlzm_hip_decode_finish(nullptr, &total); open = false; }
-                if (open) nlzm_hip_decode_abandon();
-                if (by_index && (drc == NLZM_HIP_E_CAPACITY || drc == NLZM_HIP_E_FORMAT || drc == NLZM_HIP_E_NOMEM)) { index_wrong = true; drc = 0; }
-                if (drc == NLZM_HIP_E_FORMAT) rc = -7;
-                else if (drc) { printf("Error: %s\n", nlzm_hip_last_error()); if (fout) { fclose(fout); remove(argv[3]); } return -1; }
-                hb = parts[0].p[1]; fb = parts[0].p[3];
-                // (a decode that did not come to its end leaves nothing of what its steps wrote: the one-call path writes nothing then either)
-                if ((index_wrong || rc) && fout) { fflush(fout); if (ftruncate(fileno(fout), 0)) {} fseeko(fout, 0, SEEK_SET); }
-                if (!index_wrong && !rc) {
-                    if (k > 1) printf("Blocks: %d\n", (int)k);
-                    printf("Steps: %u frames, %" PRIu64 " launches\n", steps_k, launches);
-                    if (fout) { fflush(fout); if (ftruncate(fileno(fout), (off_t)total)) {} fseeko(fout, 0, SEEK_END); }
-                    raws = raw; got_crcs = crcs; out_size = total; out_on_device = true;        // (nothing of the output is left on the host: its CRC32 is the blocks' combined)
-                }
-            } else if (!rc && on_gpu && idx_has_crc && cmd == 't' && !typed) {
-                // nlzm_hip_check: decoded into a buffer on the device, every block bounded by its index entry, and hashed there
-                const uint32_t k = (uint32_t)parts.size();
-                std::vector<uint64_t> blen(k), raw(k);
-                for (uint32_t i = 0; i < k; i++) blen[i] = parts[i].n;
-                const uint64_t src_len = (uint64_t)(parts.back().p + parts.back().n - parts[0].p);
-                uint32_t first_bad = k;
-                got_crcs.assign(k, 0);
-                int drc = nlzm_hip_check(parts[0].p, src_len, k, blen.data(), raws.data(), idx_crcs.data(), &first_bad, got_crcs.data());
-                if (!drc && first_bad < k) {
-                    // a wrong length or a wrong CRC?  The blocks' own lengths say (a size pass; only a container that fails pays for it)
-                    uint64_t total = 0;
-                    drc = nlzm_hip_decompress_blocks(parts[0].p, src_len, k, blen.data(), nullptr, nullptr, 0, raw.data(), &total);
-                    for (uint32_t i = 0; !drc && i < k; i++) if (raw[i] != raws[i]) index_wrong = true;
-                }
-                if (drc == NLZM_HIP_E_NOMEM) { index_wrong = true; drc = 0; }
-                if (drc == NLZM_HIP_E_FORMAT) rc = -7;
-                else if (drc) { printf("Error: %s\n", nlzm_hip_last_error()); return -1; }
-                hb = parts[0].p[1]; fb = parts[0].p[3];
-                for (uint32_t i = 0; i < k; i++) out_size += raws[i];
-                out_on_device = true;
-                if (!index_wrong && !rc && k > 1) printf("Blocks: %d\n", (int)k);
-                if (index_wrong || rc) { out_size = 0; got_crcs.clear(); }
-            } else if (!rc && on_gpu) {
-                // all blocks at once on the device, one workgroup each; boundaries from above, raw lengths from the index where it gave them
-                std::vector<uint64_t> blen(parts.size()), raw(parts.size());
-                for (size_t i = 0; i < parts.size(); i++) blen[i] = parts[i].n;
-                const uint64_t src_len = (uint64_t)(parts.back().p + parts.back().n - parts[0].p);
-                uint64_t total = 0;
-                int drc = 0;
-                if (by_index) {
-                    // the index says what every block holds: one decode pass, every block bounded by its entry -- a block that decodes to more
-                    // (NLZM_HIP_E_CAPACITY) or to less (NLZM_HIP_E_FORMAT) than that shows the index to be wrong, and the frame headers decide
-                    // (the sizes are the index's word and nothing else yet: an index that asks for more memory than the host or the device has is a
-                    //  wrong index, not a reason to die)
-                    for (size_t i = 0; i < parts.size(); i++) total += raws[i];
-                    bool room = true;
-                    try { out.resize((size_t)total); } catch (const std::exception &) { room = false; }
-                    if (room && typed) drc = nlzm_hip_decompress_blocks_typed(parts[0].p, src_len, (uint32_t)parts.size(), blen.data(), raws.data(), idx_elems.data(), out.data(), total, raw.data(), &total);
-                    else if (room) drc = nlzm_hip_decompress_blocks(parts[0].p, src_len, (uint32_t)parts.size(), blen.data(), raws.data(), out.data(), total, raw.data(), &total);
-                    if (!room || drc == NLZM_HIP_E_CAPACITY || drc == NLZM_HIP_E_FORMAT || drc == NLZM_HIP_E_NOMEM) { index_wrong = true; drc = 0; std::vector<uint8_t>().swap(out); }
-                } else {
-                    // no lengths anywhere in the format: a size pass, then the decode
-                    drc = nlzm_hip_decompress_blocks(parts[0].p, src_len, (uint32_t)parts.size(), blen.data(), nullptr, nullptr, 0, raw.data(), &total);
-                    if (!drc) {
-                        out.resize((size_t)total);
-                        drc = nlzm_hip_decompress_blocks(parts[0].p, src_len, (uint32_t)parts.size(), blen.data(), raw.data(), out.data(), total, nullptr, &total);
-                    }
-                }
-                if (drc == NLZM_HIP_E_FORMAT) rc = -7;
-                else if (drc) { printf("Error: %s\n", nlzm_hip_last_error()); if (fout) { fclose(fout); remove(argv[3]); } return -1; }
-                hb = parts[0].p[1]; fb = parts[0].p[3];
-                if (parts.size() > 1) printf("Blocks: %d\n", (int)parts.size());
-            } else if (parts.size() == 1) {
-                rc = decode_stream(parts[0], out, &hb, &fb);
-                if (!rc && by_index && out.size() != raws[0]) index_wrong = true;
-            } else if (!rc) {
-                std::vector<std::vector<uint8_t>> outs(parts.size());
-                std::vector<int> rcs(parts.size(), 0);
-                std::vector<uint32_t> hbs(parts.size(), 0), fbs(parts.size(), 0);
-                std::vector<std::thread> th;
-                if (idx_has_crc) got_crcs.assign(parts.size(), 0);
-                for (size_t i = 0; i < parts.size(); i++)
-                    th.emplace_back([&, i] {
-                        rcs[i] = decode_stream(parts[i], outs[i], &hbs[i], &fbs[i]);
-                        if (!rcs[i] && idx_has_crc) got_crcs[i] = crc_calc(outs[i].data(), outs[i].size(), 0);
-                    });
-                for (auto &t : th) t.join();
-                for (size_t i = 0; i < parts.size() && !rc; i++) {
-                    rc = rcs[i];
-                    if (!rc && by_index && outs[i].size() != raws[i]) index_wrong = true;
-                    out.insert(out.end(), outs[i].begin(), outs[i].end());
-                }
-                hb = hbs[0]; fb = fbs[0];
-                if (!index_wrong) printf("Blocks: %d\n", (int)parts.size());
-            }
-            if (typed && !on_gpu && !rc && !index_wrong) {
-                // host-only: the planes undone block by block, by the rule restated above; the CRC32s are the raw bytes', hashed below
-                std::vector<uint8_t> raw_bytes(out.size());
-                std::vector<std::thread> th;
-                uint64_t at = 0;
-                for (size_t i = 0; i < parts.size(); i++) { th.emplace_back([&, i, at] { planes_undo(out.data() + at, raw_bytes.data() + at, raws[i], idx_elems[i]); }); at += raws[i]; }
-                for (auto &t : th) t.join();
-                out.swap(raw_bytes);
-                got_crcs.clear();
-            }
-            if (!(by_index && (index_wrong || rc))) break;
-            // the index passed its checks and still does not describe these streams (stale, or of another file): the frame headers decide
-            printf("Note: %s.idx does not describe this file's blocks; they are found by their frame headers\n", argv[2]);
-        }
-        if (rc) { printf("Assert failed: malformed stream (%d)\n", rc); if (fout) fclose(fout); return -1; }
-        const bool check_crc = by_index && idx_has_crc;
-        if (check_crc && got_crcs.empty()) {
-            // one stream, or d -gpu: the bytes are on the host, hashed there block by block
-            got_crcs.assign(parts.size(), 0);
-            std::vector<std::thread> th;
-            uint64_t at = 0;
-            for (size_t i = 0; i < parts.size(); i++) { th.emplace_back([&, i, at] { got_crcs[i] = crc_calc(out.data() + at, raws[i], 0); }); at += raws[i]; }
-            for (auto &t : th) t.join();
-        }
-        uint32_t out_crc = 0;
-        if (out_on_device) for (size_t i = 0; i < parts.size(); i++) out_crc = nlzm_hip_crc32_combine(out_crc, got_crcs[i], raws[i]);
-        else { out_crc = crc_calc(out.data(), out.size(), 0); out_size = out.size(); }
-        printf("Dictionary: %d KB\n", (int)(((1ull << hb) + 1023) >> 10));
-        printf("Frame: %d KB\n", (int)(((1u << fb) + 1023) >> 10));
-        if (fout) { fwrite(out.data(), 1, out.size(), fout); fclose(fout); }
-        printf("Working... %" PRIu64 " -> %" PRIu64 "\n", (uint64_t)in.size(), out_size);
-        printf("Done (output CRC32 %X, %.2f sec)\n", out_crc, (clock() - t0) / (double)CLOCKS_PER_SEC);
-        bool crc_bad = false;
-        if (check_crc) {
-            // the index's CRCs against what decoded: every block, then -- where the container is whole -- their combination against the file's
-            uint32_t comb = 0;
-            for (size_t i = 0; i < parts.size(); i++) comb = nlzm_hip_crc32_combine(comb, got_crcs[i], raws[i]);
-            for (size_t i = 0; i < parts.size() && !crc_bad; i++)
-                if (got_crcs[i] != idx_crcs[i]) { printf("CRC32 MISMATCH in block %zu (index says %08X, decoded %08X)\n", i + 1, idx_crcs[i], got_crcs[i]); crc_bad = true; }
-            if (!crc_bad && !cut_tail && comb != idx_whole) { printf("CRC32 MISMATCH of the whole file (index says %08X, blocks combine to %08X)\n", idx_whole, comb); crc_bad = true; }
-            if (!crc_bad) printf("CRC32 ok (%zu blocks)\n", parts.size());
-            else if (fout) printf("Note: %s holds what decoded\n", argv[3]);
-        }
-        if (cut_tail) { printf("Error: the container is cut off inside block %zu (%zu bytes of it present); %zu complete blocks decoded\n", parts.size() + 1, cut_tail, parts.size()); return -2; }
-        if (crc_bad) return -4;
-    } else if (argc == 4 && cmd == 'x' && !ranges.empty()) {
-        return extract(argv[2], argv[3], ranges, on_gpu);
-    } else if (argc == 3 && cmd == 'h') {
-        std::vector<uint8_t> in;
-        if (!slurp(argv[2], in)) { printf("Error: %s file does not exist\n", argv[2]); return -1; }
-        uint32_t crc = 0;
-        if (on_gpu) {
-            if (nlzm_hip_init(0) || nlzm_hip_crc32(in.data(), in.size(), 0, &crc)) { printf("Error: %s\n", nlzm_hip_last_error()); return -1; }
-            nlzm_hip_shutdown();
-        } else crc = crc_calc(in.data(), in.size(), 0);
-        printf("%X\n", crc);
-    } else {
-        printf("Commands:\n"
-               "\t[flags] c [input] [output] - Compress input file to output file (best parser)\n"
-               "\td [input] [output] - Decompress input file to output file\n"
-               "\tt [input] - Decompress input file in memory\n"
-               "\th [input] - Calculate CRC32 for input file\n"
-               "\t-range:off:len [-range:...] x [input] [output] - (this build) write those byte ranges of what a block container holds; needs [input].idx\n"
-               "Flags:\n"
-               "\t-window:bits = Maximum window size in bits, default 22 (4 MB), min 15, max 28 (32 KB to 256 MB)\n"
-               "\t-blocks:k = (this build) compress k independent blocks, 1 to 65536: as many at once as a launch holds (64), more of them\n"
-               "\t            in sets one after another; d/t read the streams back to back\n"
-               "\t-cdc:B = (this build) c cuts the blocks by content on the GPU, 2^B bytes on average (B 10 to 30): an edit changes the blocks around it only\n"
-               "\t-elem:E = (this build) c compresses every block's byte planes at element size E (2, 4 or 8), alone or with -blocks:k / -cdc:B, and writes NLZMIDX 3; d / t undo them\n"
-               "\t-dedup = (this build) with -cdc:B: a block whose bytes an earlier block holds is not compressed again, its stream is a copy (the same container)\n"
-               "\t-gpus:g = (this build) the blocks on GPUs 0..g-1 of this node, -blocks:k of them on each (64 at most)\n"
-               "\t-verify = (this build) c decodes what it wrote on the GPU, one workgroup per stream, compares it with the input\n"
-               "\t          and removes the output if they differ\n"
-               "\t-gpu = (this build) d / t decode on the GPU, all blocks of a container at once (without it they run on the host); h hashes there\n"
-               "\t-steps:K = (this build) d -gpu / t -gpu decode in steps of K frames per block; d writes every step's bytes as they come\n"
-               "\t-crc = (this build) c hashes every block on the GPU and keeps the CRC32s in [output].idx (NLZMIDX 2), for one stream too;\n"
-               "\t       d / t compare what they decode with an index that holds CRC32s and exit with status -4 if a block differs\n");
+        if (refuse_existing(argv[3])) return -1;
+        const bool one_stream = !o.ngpus && o.nblocks == 1 && !o.verify && !o.cdc_bits && !o.elem;
+        return one_stream ? compress_one_stream(o, argv[2], argv[3]) : compress_container(o, argv[2], argv[3]);
     }
+    if (decodes) return decode(o, cmd == 'd', argv[2], cmd == 'd' ? argv[3] : nullptr);
+    if (argc == 4 && cmd == 'x' && !o.ranges.empty()) return extract(argv[2], argv[3], o.ranges, o.on_gpu);
+    if (argc == 3 && cmd == 'h') return hash(argv[2], o.on_gpu);
+    usage();
     return 0;
 }

@@ -11,6 +11,7 @@ import pytest
 import nlzm_amd
 from nlzm_amd import corpus, shard
 from tests import oracle_py
+from tests.cli_tools import cli, write_index
 
 ROOT = os.path.dirname(os.path.abspath(__file__ + "/.."))
 E_NODEVICE = -2
@@ -102,18 +103,6 @@ def container(lib):
     return {"data": raw, "ranges": ranges, "streams": streams, "crcs": [zlib.crc32(raw[lo:hi]) for lo, hi in ranges], "whole": zlib.crc32(raw)}
 
 
-def write_index(path, streams, raws, crcs, whole, n_in=None, version=2):
-    off, lines = 0, [f"NLZMIDX {version} {len(streams)} {sum(raws) if n_in is None else n_in} {sum(map(len, streams))} {whole:08X}"]
-    for s, raw, c in zip(streams, raws, crcs):
-        lines.append(f"{off} {len(s)} {raw} {c:08X}")
-        off += len(s)
-    path.write_text("\n".join(lines) + "\n")
-
-
-def cli(*args):
-    return subprocess.run([nlzm_amd.CLI_PATH] + [str(a) for a in args], capture_output=True, text=True)
-
-
 def test_cli_good_index_with_crcs(tmp_path, container):
     c = container
     f = tmp_path / "c.nlzm"
@@ -187,10 +176,6 @@ def test_cli_index_with_crcs_that_does_not_fit(tmp_path, container):
     assert r.returncode == 0 and "does not describe" in r.stdout and "CRC32 ok" not in r.stdout and "MISMATCH" not in r.stdout, r.stdout
     assert out.read_bytes() == c["data"]
     # a version-1 index is read as before
-    off, lines = 0, [f"NLZMIDX 1 {K} {sum(raws)} {sum(map(len, c['streams']))}"]
-    for s, raw in zip(c["streams"], raws):
-        lines.append(f"{off} {len(s)} {raw}")
-        off += len(s)
-    (tmp_path / "c.nlzm.idx").write_text("\n".join(lines) + "\n")
+    write_index(tmp_path / "c.nlzm.idx", c["streams"], raws, version=1)
     r = cli("t", f)
     assert r.returncode == 0 and "does not" not in r.stdout and "CRC32 ok" not in r.stdout and f"Blocks: {K}" in r.stdout, r.stdout

@@ -8,7 +8,7 @@ import pytest
 
 import nlzm_amd
 from nlzm_amd import corpus, shard
-from tests import oracle_py
+from tests import cli_tools, oracle_py
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 E_NODEVICE = -2
@@ -96,11 +96,7 @@ def test_cli_block_index_that_lies(tmp_path, lib):
     f.write_bytes(blob)
 
     def write_index(lens, raws):
-        off, lines = 0, [f"NLZMIDX 1 {k} {data.size} {len(blob)}"]
-        for ln, raw in zip(lens, raws):
-            lines.append(f"{off} {ln} {raw}")
-            off = (off + ln) % (1 << 64)
-        idx.write_text("\n".join(lines) + "\n")
+        cli_tools.write_index(idx, lens, raws, version=1, n_in=data.size, n_out=len(blob))
 
     good_lens, good_raws = [len(s) for s in streams], [hi - lo for lo, hi in ranges]
     # block 2's length wraps offset + length round to a small number

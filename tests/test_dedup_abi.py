@@ -9,6 +9,7 @@ import subprocess
 import pytest
 
 import nlzm_amd
+from tests.cli_tools import cli
 
 ROOT = os.path.dirname(os.path.abspath(__file__ + "/.."))
 E_ARG, E_NODEVICE = -1, -2
@@ -138,10 +139,6 @@ def test_library_has_the_dedup_kernels(lib):
     blob = open(nlzm_amd.LIB_PATH, "rb").read()
     for name in KERNELS:
         assert name.encode() in blob, name
-
-
-def cli(*args):
-    return subprocess.run([nlzm_amd.CLI_PATH] + [str(a) for a in args], capture_output=True, text=True)
 
 
 def test_cli_usage_and_conflicts(lib, tmp_path):

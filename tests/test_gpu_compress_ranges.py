@@ -2,7 +2,6 @@
 on what they make, and the command line's -cdc:B.  Every check is exact.  Inputs are at most 600 KB; only streams a compressor made are
 handed to the device."""
 import ctypes as C
-import subprocess
 import zlib
 
 import numpy as np
@@ -12,6 +11,7 @@ import torch        # (before the library is loaded, as bench.py has it: both th
 import nlzm_amd
 from nlzm_amd import corpus, shard
 from tests import cut_model, oracle_py
+from tests.cli_tools import cli
 
 pytestmark = pytest.mark.gpu
 
@@ -113,10 +113,6 @@ def test_round_trip_through_the_read_side(gpu, nine):
     crcs = [zlib.crc32(raw[o:o + l]) for o, l in ranges]
     assert gpu.read_ranges(blob, want, k, lens, raws, crcs) == [content[o:o + l] for o, l in want]
     assert gpu.check(blob, crcs, k, raws) == k
-
-
-def cli(*args):
-    return subprocess.run([nlzm_amd.CLI_PATH] + [str(a) for a in args], capture_output=True, text=True)
 
 
 def test_cli_cdc(gpu, tmp_path):

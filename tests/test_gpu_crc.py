@@ -2,7 +2,6 @@
 against CRCs without its original.  Only streams a compressor made are handed to the device, as in tests/test_gpu_decode.py."""
 import ctypes as C
 import re
-import subprocess
 import zlib
 
 import numpy as np
@@ -11,6 +10,7 @@ import torch        # (before the library is loaded, as bench.py has it: both th
 
 import nlzm_amd
 from nlzm_amd import corpus, shard
+from tests.cli_tools import cli
 
 pytestmark = pytest.mark.gpu
 
@@ -168,9 +168,6 @@ def test_cli_crc(gpu, tmp_path):
     raw = data.tobytes()
     src = tmp_path / "in.bin"
     data.tofile(src)
-
-    def cli(*args):
-        return subprocess.run([nlzm_amd.CLI_PATH] + [str(a) for a in args], capture_output=True, text=True)
 
     plain, with_crc = tmp_path / "plain.nlzm", tmp_path / "crc.nlzm"
     r = cli("-window:18", f"-blocks:{k}", "c", src, plain)

@@ -4,7 +4,6 @@ path with option "dedup_ranges" against the same call without it and against the
 compressor made are handed to the device."""
 import ctypes as C
 import re
-import subprocess
 
 import numpy as np
 import pytest
@@ -13,6 +12,7 @@ import torch        # (before the library is loaded, as bench.py has it: both th
 import nlzm_amd
 from nlzm_amd import corpus
 from tests import cut_model, dedup_model, oracle_py
+from tests.cli_tools import cli
 
 pytestmark = pytest.mark.gpu
 
@@ -218,10 +218,6 @@ def test_errors_with_the_option_on_and_the_call_after(gpu, awkward):
         assert lib.nlzm_hip_blocks_step(0, None, None, None) == E_ARG         # (the call has closed its set)
     finally:
         gpu.set_option("dedup_ranges", 0)
-
-
-def cli(*args):
-    return subprocess.run([nlzm_amd.CLI_PATH] + [str(a) for a in args], capture_output=True, text=True)
 
 
 def test_cli_dedup(gpu, tmp_path):

@@ -2,7 +2,6 @@
 against the numpy model (tests/planes_model.py) and the oracle run on the model's planes, the torch binding, and the command line's -elem:E.
 Every check is exact.  Inputs are under 300 KB; only streams a compressor made are handed to the device."""
 import ctypes as C
-import subprocess
 import zlib
 
 import numpy as np
@@ -12,6 +11,7 @@ import torch        # (before the library is loaded, as bench.py has it: both th
 import nlzm_amd
 from nlzm_amd import corpus
 from tests import oracle_py, planes_model
+from tests.cli_tools import cli
 
 pytestmark = pytest.mark.gpu
 
@@ -210,10 +210,6 @@ def test_tensors_round_trip(gpu):
         assert torch.equal(r.cpu().view(torch.uint8), t.cpu().contiguous().view(torch.uint8))
     tied, meta2 = gpu.compress_tensors(tensors, HIST, dedup=True)
     assert torch.equal(tied, container) and meta2 == meta and gpu.counter("dedup_distinct") == 4 and gpu.counter("dedup_ranges") == 0
-
-
-def cli(*args):
-    return subprocess.run([nlzm_amd.CLI_PATH] + [str(a) for a in args], capture_output=True, text=True)
 
 
 def test_cli_elem(gpu, tmp_path):

@@ -14,6 +14,7 @@ import pytest
 import nlzm_amd
 from nlzm_amd import corpus
 from tests import oracle_py, planes_model
+from tests.cli_tools import cli, write_index
 
 ROOT = os.path.dirname(os.path.abspath(__file__ + "/.."))
 E_ARG, E_NODEVICE = -1, -2
@@ -185,14 +186,8 @@ def container(lib):
     return {"blocks": blocks, "elems": elems, "streams": streams, "crcs": [zlib.crc32(b) for b in blocks], "whole": zlib.crc32(b"".join(blocks))}
 
 
-def write_index3(path, c, elems=None, crcs=None, n_in=None, n_out=None, offs=None, whole=None):
-    lens, raws = [len(s) for s in c["streams"]], [len(b) for b in c["blocks"]]
-    lines = [f"NLZMIDX 3 {len(lens)} {sum(raws) if n_in is None else n_in} {sum(lens) if n_out is None else n_out} {c['whole'] if whole is None else whole:08X}"]
-    off = 0
-    for i in range(len(lens)):
-        lines.append(f"{off if offs is None else offs[i]} {lens[i]} {raws[i]} {(crcs or c['crcs'])[i]:08X} {(elems or c['elems'])[i]}")
-        off += lens[i]
-    path.write_text("\n".join(lines) + "\n")
+def write_index3(path, c, elems=None, crcs=None, whole=None, **kw):
+    write_index(path, c["streams"], [len(b) for b in c["blocks"]], crcs or c["crcs"], c["whole"] if whole is None else whole, version=3, elems=elems or c["elems"], **kw)
 
 
 def test_read_index_typed(tmp_path, container):
@@ -233,10 +228,6 @@ def test_read_index_typed(tmp_path, container):
         p.write_text(text)
         with pytest.raises(ValueError):
             nlzm_amd.read_index_typed(p)
-
-
-def cli(*args):
-    return subprocess.run([nlzm_amd.CLI_PATH] + [str(a) for a in args], capture_output=True, text=True)
 
 
 def test_cli_usage_and_conflicts(lib, tmp_path):

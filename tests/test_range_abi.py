@@ -12,6 +12,7 @@ import pytest
 import nlzm_amd
 from nlzm_amd import corpus
 from tests import oracle_py
+from tests.cli_tools import cli, write_index
 
 ROOT = os.path.dirname(os.path.abspath(__file__ + "/.."))
 E_NODEVICE = -2
@@ -81,16 +82,6 @@ def container(lib):
     return {"data": raw, "starts": starts, "streams": streams, "crcs": [zlib.crc32(b) for b in blocks], "whole": zlib.crc32(raw)}
 
 
-def write_index(path, streams, raws, crcs, whole, version=2, n_in=None, n_out=None, offs=None):
-    off = 0
-    head = f"NLZMIDX {version} {len(streams)} {sum(raws) if n_in is None else n_in} {sum(map(len, streams)) if n_out is None else n_out}"
-    lines = [head + (f" {whole:08X}" if version == 2 else "")]
-    for i, (s, raw, c) in enumerate(zip(streams, raws, crcs)):
-        lines.append(f"{off if offs is None else offs[i]} {len(s) if isinstance(s, bytes) else s} {raw}" + (f" {c:08X}" if version == 2 else ""))
-        off += len(s) if isinstance(s, bytes) else s
-    path.write_text("\n".join(lines) + "\n")
-
-
 def test_read_index(tmp_path, container):
     c = container
     p = tmp_path / "c.idx"
@@ -122,10 +113,6 @@ def test_read_index(tmp_path, container):
     p.write_text("NLZMIDX 3 1 10 8\n0 8 10\n")
     with pytest.raises(ValueError):
         nlzm_amd.read_index(p)
-
-
-def cli(*args):
-    return subprocess.run([nlzm_amd.CLI_PATH] + [str(a) for a in args], capture_output=True, text=True)
 
 
 def setup(tmp_path, c, crcs=None, cut=None):
