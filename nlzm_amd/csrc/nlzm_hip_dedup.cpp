@@ -39,14 +39,7 @@ int check_args(uint64_t buf_len, uint32_t k, const uint64_t *off, const uint64_t
     return 0;
 }
 
-// a prefix table of units per entry: table[i + 1] - table[i] = ceil(len(i) / unit)
-template <class Len>
-std::vector<unsigned long long> prefix_of(uint32_t n, unsigned long long unit, Len len)
-{
-    std::vector<unsigned long long> t((size_t)n + 1, 0);
-    for (uint32_t i = 0; i < n; i++) t[i + 1] = t[i] + len(i) / unit + (len(i) % unit ? 1 : 0);
-    return t;
-}
+using dedup::prefix_of;      // (nlzm_dedup_plan.h)
 
 // one round's pairs on the device: equal[p] for every pair
 int compare_pairs(hipStream_t st, const void *d_buf, const uint64_t *off, const uint64_t *len, const std::vector<dedup::IndexPair> &pairs, std::vector<uint8_t> &equal, double *us)
