@@ -23,6 +23,7 @@
 #pragma once
 
 #include "xw.h"
+#include "nlzm_units.h"
 
 #ifndef NLZM_SIM
 #define CRC_HD __host__ __device__ inline      // (arithmetic the host side uses too: nlzm_hip_crc32_combine)
@@ -196,8 +197,7 @@ XW_FN void segments_role(const Args &a, uint32_t nthreads, unsigned long long w,
     Lds *L = xw::lds<Lds>();
     build_tables(L, nthreads);
     for (unsigned long long g = w; g < a.nsegs; g += nwaves) {
-        uint32_t lo = 0, hi = a.nranges;            // the range whose segments hold g: the last r with seg0[r] <= g
-        while (hi - lo > 1) { const uint32_t m = lo + (hi - lo) / 2; if (a.seg0[m] <= g) lo = m; else hi = m; }
+        const uint32_t lo = units::owner_of(a.seg0, a.nranges, g);         // the range whose segments hold g
         const unsigned long long j = g - a.seg0[lo], at = j * kSegment, left = a.len[lo] - at;
         const uint32_t s = segment_state(L, a.buf + a.off[lo] + at, left < kSegment ? left : kSegment, j ? 0u : ~a.seed);
         if (xw::lane() == 0) a.part[g] = s;

@@ -6,6 +6,7 @@
 
 #include "nlzm_cut_host.h"
 #include "nlzm_cut.h"
+#include "nlzm_units.h"
 
 namespace nlzm {
 __shared__ cut::Lds g_cut_lds;
@@ -15,24 +16,22 @@ template <class T> XW_FN T *lds() { return reinterpret_cast<T *>(&nlzm::g_cut_ld
 }
 namespace nlzm {
 
-#define NLZM_G(T, x) ((T *)(__attribute__((address_space(1))) T *)(unsigned long long)(x))      // (pointers handed over in a struct: global ones, not flat)
-
 constexpr uint32_t kCutThreads = 64;
 
-__device__ __forceinline__ cut::Args global_args(cut::Args a)
+__device__ __forceinline__ cut::Args global_args(cut::Args a)               // (pointers handed over in a struct: global ones, not flat)
 {
-    a.src = NLZM_G(const uint8_t, a.src);
-    a.bits = NLZM_G(uint32_t, a.bits);
-    a.count = NLZM_G(uint32_t, a.count);
-    a.cut = NLZM_G(unsigned long long, a.cut);
-    a.res = NLZM_G(unsigned long long, a.res);
+    a.src = NLZM_GLOBAL(const uint8_t, a.src);
+    a.bits = NLZM_GLOBAL(uint32_t, a.bits);
+    a.count = NLZM_GLOBAL(uint32_t, a.count);
+    a.cut = NLZM_GLOBAL(unsigned long long, a.cut);
+    a.res = NLZM_GLOBAL(unsigned long long, a.res);
     return a;
 }
 
 __global__ __launch_bounds__(kCutThreads) void cut_scan_kernel(cut::Args args)
 {
     const cut::Args a = global_args(args);
-    cut::scan_role(a, kCutThreads, blockIdx.x, gridDim.x);
+    cut::scan_role(a, kCutThreads, blockIdx.x, gridDim.x);      // (one wave a workgroup: the workgroup's index is the wave's)
 }
 
 __global__ __launch_bounds__(kCutThreads) void cut_select_kernel(cut::Args args)
@@ -45,7 +44,7 @@ __global__ __launch_bounds__(kCutThreads) void cut_select_kernel(cut::Args args)
 void launch_cut(const cut::Args &a, uint32_t max_blocks, hipStream_t st)
 {
     if (!a.nsegs) return;
-    hipLaunchKernelGGL(cut_scan_kernel, dim3((uint32_t)(a.nsegs < max_blocks ? a.nsegs : max_blocks)), dim3(kCutThreads), 0, st, a);
+    hipLaunchKernelGGL(cut_scan_kernel, units::grid<kCutThreads>(a.nsegs, max_blocks), dim3(kCutThreads), 0, st, a);
     hipLaunchKernelGGL(cut_select_kernel, dim3(1), dim3(kCutThreads), 0, st, a);
 }
 

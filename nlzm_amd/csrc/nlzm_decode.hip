@@ -6,6 +6,7 @@
 #include <stdint.h>
 
 #include "nlzm_decode.h"
+#include "nlzm_units.h"
 
 namespace nlzm {
 // the stream's output ring: a file-scope __shared__ object, every access is a ds_* instruction
@@ -16,14 +17,13 @@ template <class T> XW_FN T *lds() { return reinterpret_cast<T *>(&nlzm::g_dec_ld
 }
 namespace nlzm {
 
-#define NLZM_G(T, x) ((T *)(__attribute__((address_space(1))) T *)(unsigned long long)(x))      // (pointers read from memory: global ones, not flat)
 
 // Workgroup b decodes stream b.  More streams than the device has room for wait in the dispatcher and start as workgroups end.
 __global__ __launch_bounds__(64) void decode_kernel(const dec::StreamArgs *__restrict__ args, dec::StreamResult *__restrict__ res)
 {
     dec::StreamArgs a = args[blockIdx.x];
-    a.src = NLZM_G(const uint8_t, a.src);
-    a.dst = NLZM_G(uint8_t, a.dst);
+    a.src = NLZM_GLOBAL(const uint8_t, a.src);
+    a.dst = NLZM_GLOBAL(uint8_t, a.dst);
     dec::decode_role(a, res + blockIdx.x);
 }
 
@@ -32,9 +32,9 @@ __global__ __launch_bounds__(64) void decode_kernel(const dec::StreamArgs *__res
 __global__ __launch_bounds__(64) void decode_steps_kernel(const dec::StreamArgs *__restrict__ args, dec::StreamResult *__restrict__ res)
 {
     dec::StreamArgs a = args[blockIdx.x];
-    a.src = NLZM_G(const uint8_t, a.src);
-    a.dst = NLZM_G(uint8_t, a.dst);
-    a.state = NLZM_G(dec::StepState, a.state);
+    a.src = NLZM_GLOBAL(const uint8_t, a.src);
+    a.dst = NLZM_GLOBAL(uint8_t, a.dst);
+    a.state = NLZM_GLOBAL(dec::StepState, a.state);
     dec::decode_role_steps(a, res + blockIdx.x);
 }
 

@@ -12,6 +12,7 @@
 #define NLZM_DEC_RING 16384
 #endif
 #include "nlzm_decode.h"
+#include "nlzm_units.h"
 
 namespace nlzm {
 // the stream's output ring: a file-scope __shared__ object, every access is a ds_* instruction
@@ -22,14 +23,13 @@ template <class T> XW_FN T *lds() { return reinterpret_cast<T *>(&nlzm::g_dec_sm
 }
 namespace nlzm {
 
-#define NLZM_G(T, x) ((T *)(__attribute__((address_space(1))) T *)(unsigned long long)(x))      // (pointers read from memory: global ones, not flat)
 
 // Workgroup b decodes stream b, as in decode_kernel.
 __global__ __launch_bounds__(64) void decode_small_kernel(const dec_small::StreamArgs *__restrict__ args, dec_small::StreamResult *__restrict__ res)
 {
     dec_small::StreamArgs a = args[blockIdx.x];
-    a.src = NLZM_G(const uint8_t, a.src);
-    a.dst = NLZM_G(uint8_t, a.dst);
+    a.src = NLZM_GLOBAL(const uint8_t, a.src);
+    a.dst = NLZM_GLOBAL(uint8_t, a.dst);
     dec_small::decode_role(a, res + blockIdx.x);
 }
 

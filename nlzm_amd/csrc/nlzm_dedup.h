@@ -28,6 +28,7 @@
 #pragma once
 
 #include "xw.h"
+#include "nlzm_units.h"
 
 namespace nlzm {
 namespace dedup {
@@ -92,13 +93,6 @@ XW_FN unsigned long long wave_add64(unsigned long long v)
     for (uint32_t d = 1; d < 64; d <<= 1) v += xw::shfl64(v, l ^ d);
     return v;
 }
-// the last r < n with table[r] <= s (table[0] = 0 <= s; entries that own nothing repeat their successor's start)
-XW_FN uint32_t owner_of(const unsigned long long *table, uint32_t n, unsigned long long s)
-{
-    uint32_t lo = 0, hi = n;
-    while (hi - lo > 1) { const uint32_t m = lo + (hi - lo) / 2; if (table[m] <= s) lo = m; else hi = m; }
-    return lo;
-}
 
 // h of the m bytes at p (1 <= m <= kSegment) by one wave (wave-uniform arguments); every lane returns it
 XW_FN unsigned long long segment_h(const uint8_t *p, uint32_t m)
@@ -130,7 +124,7 @@ XW_FN unsigned long long segment_h(const uint8_t *p, uint32_t m)
 XW_FN void fingerprint_role(const FpArgs &a, unsigned long long w, unsigned long long nwaves)
 {
     for (unsigned long long s = w; s < a.nsegs; s += nwaves) {
-        const uint32_t r = owner_of(a.seg0, a.k, s);
+        const uint32_t r = units::owner_of(a.seg0, a.k, s);
         const unsigned long long at = (s - a.seg0[r]) * kSegment, left = a.len[r] - at;
         const unsigned long long h = segment_h(a.buf + a.off[r] + at, (uint32_t)(left < kSegment ? left : kSegment));
         if (xw::lane() == 0) a.seg_h[s] = h;
@@ -175,7 +169,7 @@ XW_FN bool chunk_differs(const uint8_t *x, const uint8_t *y, uint32_t n)
 XW_FN void pair_role(const PairArgs &a, unsigned long long w, unsigned long long nwaves)
 {
     for (unsigned long long c = w; c < a.nchunks; c += nwaves) {
-        const uint32_t p = owner_of(a.chunk0, a.npairs, c);
+        const uint32_t p = units::owner_of(a.chunk0, a.npairs, c);
         const Pair P = a.pairs[p];
         const unsigned long long at = (c - a.chunk0[p]) * kChunk, left = P.len - at;
         const bool ne = chunk_differs(a.buf + P.a + at, a.buf + P.b + at, (uint32_t)(left < kChunk ? left : kChunk));

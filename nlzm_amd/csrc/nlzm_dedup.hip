@@ -8,75 +8,63 @@
 
 namespace nlzm {
 
-#define NLZM_G(T, x) ((T *)(__attribute__((address_space(1))) T *)(unsigned long long)(x))      // (pointers handed over in a struct: global ones, not flat)
-
 constexpr uint32_t kDedupThreads = 256;
-constexpr uint32_t kDedupWaves = kDedupThreads / 64;
 
-__device__ __forceinline__ dedup::FpArgs global_args(dedup::FpArgs a)
+__device__ __forceinline__ dedup::FpArgs global_args(dedup::FpArgs a)       // (pointers handed over in a struct: global ones, not flat)
 {
-    a.buf = NLZM_G(const uint8_t, a.buf);
-    a.off = NLZM_G(const unsigned long long, a.off);
-    a.len = NLZM_G(const unsigned long long, a.len);
-    a.seg0 = NLZM_G(const unsigned long long, a.seg0);
-    a.seg_h = NLZM_G(unsigned long long, a.seg_h);
-    a.fp = NLZM_G(unsigned long long, a.fp);
+    a.buf = NLZM_GLOBAL(const uint8_t, a.buf);
+    a.off = NLZM_GLOBAL(const unsigned long long, a.off);
+    a.len = NLZM_GLOBAL(const unsigned long long, a.len);
+    a.seg0 = NLZM_GLOBAL(const unsigned long long, a.seg0);
+    a.seg_h = NLZM_GLOBAL(unsigned long long, a.seg_h);
+    a.fp = NLZM_GLOBAL(unsigned long long, a.fp);
     return a;
 }
 __device__ __forceinline__ dedup::PairArgs global_args(dedup::PairArgs a)
 {
-    a.buf = NLZM_G(const uint8_t, a.buf);
-    a.pairs = NLZM_G(const dedup::Pair, a.pairs);
-    a.chunk0 = NLZM_G(const unsigned long long, a.chunk0);
-    a.chunk_ne = NLZM_G(uint32_t, a.chunk_ne);
-    a.equal = NLZM_G(uint32_t, a.equal);
+    a.buf = NLZM_GLOBAL(const uint8_t, a.buf);
+    a.pairs = NLZM_GLOBAL(const dedup::Pair, a.pairs);
+    a.chunk0 = NLZM_GLOBAL(const unsigned long long, a.chunk0);
+    a.chunk_ne = NLZM_GLOBAL(uint32_t, a.chunk_ne);
+    a.equal = NLZM_GLOBAL(uint32_t, a.equal);
     return a;
 }
-
-#define NLZM_WAVE ((unsigned long long)blockIdx.x * kDedupWaves + xw::wave())
-#define NLZM_WAVES ((unsigned long long)gridDim.x * kDedupWaves)
 
 __global__ __launch_bounds__(kDedupThreads) void dedup_fingerprint_kernel(dedup::FpArgs args)
 {
     const dedup::FpArgs a = global_args(args);
-    dedup::fingerprint_role(a, NLZM_WAVE, NLZM_WAVES);
+    dedup::fingerprint_role(a, units::wave<kDedupThreads>(), units::waves<kDedupThreads>());
 }
 __global__ __launch_bounds__(kDedupThreads) void dedup_combine_kernel(dedup::FpArgs args)
 {
     const dedup::FpArgs a = global_args(args);
-    dedup::combine_role(a, NLZM_WAVE, NLZM_WAVES);
+    dedup::combine_role(a, units::wave<kDedupThreads>(), units::waves<kDedupThreads>());
 }
 __global__ __launch_bounds__(kDedupThreads) void dedup_pair_kernel(dedup::PairArgs args)
 {
     const dedup::PairArgs a = global_args(args);
-    dedup::pair_role(a, NLZM_WAVE, NLZM_WAVES);
+    dedup::pair_role(a, units::wave<kDedupThreads>(), units::waves<kDedupThreads>());
 }
 __global__ __launch_bounds__(kDedupThreads) void dedup_verdict_kernel(dedup::PairArgs args)
 {
     const dedup::PairArgs a = global_args(args);
-    dedup::verdict_role(a, NLZM_WAVE, NLZM_WAVES);
-}
-
-static dim3 grid_for(unsigned long long waves, uint32_t max_blocks)
-{
-    const unsigned long long want = (waves + kDedupWaves - 1) / kDedupWaves;
-    return dim3((uint32_t)(want < max_blocks ? want : max_blocks));
+    dedup::verdict_role(a, units::wave<kDedupThreads>(), units::waves<kDedupThreads>());
 }
 
 // the fingerprints of all ranges of a call: every segment's sum (no segment, no launch), then every range's fingerprint
 void launch_fingerprints(const dedup::FpArgs &a, uint32_t max_blocks, hipStream_t st)
 {
     if (!a.k) return;
-    if (a.nsegs) hipLaunchKernelGGL(dedup_fingerprint_kernel, grid_for(a.nsegs, max_blocks), dim3(kDedupThreads), 0, st, a);
-    hipLaunchKernelGGL(dedup_combine_kernel, grid_for(a.k, max_blocks), dim3(kDedupThreads), 0, st, a);
+    if (a.nsegs) hipLaunchKernelGGL(dedup_fingerprint_kernel, units::grid<kDedupThreads>(a.nsegs, max_blocks), dim3(kDedupThreads), 0, st, a);
+    hipLaunchKernelGGL(dedup_combine_kernel, units::grid<kDedupThreads>(a.k, max_blocks), dim3(kDedupThreads), 0, st, a);
 }
 
 // the verdicts of all pairs of a round: every chunk's word (no chunk, no launch), then every pair's
 void launch_pairs(const dedup::PairArgs &a, uint32_t max_blocks, hipStream_t st)
 {
     if (!a.npairs) return;
-    if (a.nchunks) hipLaunchKernelGGL(dedup_pair_kernel, grid_for(a.nchunks, max_blocks), dim3(kDedupThreads), 0, st, a);
-    hipLaunchKernelGGL(dedup_verdict_kernel, grid_for(a.npairs, max_blocks), dim3(kDedupThreads), 0, st, a);
+    if (a.nchunks) hipLaunchKernelGGL(dedup_pair_kernel, units::grid<kDedupThreads>(a.nchunks, max_blocks), dim3(kDedupThreads), 0, st, a);
+    hipLaunchKernelGGL(dedup_verdict_kernel, units::grid<kDedupThreads>(a.npairs, max_blocks), dim3(kDedupThreads), 0, st, a);
 }
 
 }  // namespace nlzm

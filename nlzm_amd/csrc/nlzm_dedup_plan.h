@@ -3,7 +3,7 @@
 // one text, so that what the test proves is what the library runs.
 //
 //   dedup::check_ranges   k and every range against the buffer: a range with len > buf_len - off is NLZM_HIP_E_ARG, and the text names it
-//   dedup::prefix_of      the launches' tables: entry i owns units [t[i], t[i + 1]) -- segments of a range's fingerprint, chunks of a pair's compare
+//   (the launches' tables -- segments of a range's fingerprint, chunks of a pair's compare -- are units::prefix, nlzm_units.h)
 //   dedup::class_plan     the classes.  Two ranges with the same (off, len) are equal without a compare, and all empty ranges are equal to the first
 //                         empty one: every range stands for the smallest index of its (off, len) -- of the empty ones -- and only those take part.
 //                         They are grouped by (length, fingerprint's low hash_bits bits).  A round: in every group with two unresolved members or
@@ -39,20 +39,8 @@ inline int check_ranges(uint64_t buf_len, uint32_t k, const uint64_t *off, const
 {
     if (!k || k > kMaxRanges) return plan_error(err, NLZM_HIP_E_ARG, "%u ranges: 1 .. %u in one call", k, kMaxRanges);
     if (!off || !len) return plan_error(err, NLZM_HIP_E_ARG, "null argument");
-    for (uint32_t i = 0; i < k; i++)
-        if (off[i] > buf_len || len[i] > buf_len - off[i])      // (no off + len: it can wrap)
-            return plan_error(err, NLZM_HIP_E_ARG, "range %u (offset %llu, %llu bytes) runs over the %llu bytes of the buffer", i, (unsigned long long)off[i],
-                              (unsigned long long)len[i], (unsigned long long)buf_len);
+    for (uint32_t i = 0; i < k; i++) if (const int rc = check_in_buffer(i, off[i], len[i], buf_len, err)) return rc;
     return 0;
-}
-
-// a prefix table of units per entry: table[i + 1] - table[i] = ceil(len(i) / unit)
-template <class Len>
-std::vector<unsigned long long> prefix_of(uint32_t n, unsigned long long unit, Len len)
-{
-    std::vector<unsigned long long> t((size_t)n + 1, 0);
-    for (uint32_t i = 0; i < n; i++) t[i + 1] = t[i] + len(i) / unit + (len(i) % unit ? 1 : 0);
-    return t;
 }
 
 inline uint64_t mask_of(uint32_t hash_bits) { return hash_bits >= 64 ? ~0ull : (1ull << hash_bits) - 1; }

@@ -56,7 +56,7 @@ int crc_ranges_on(hipStream_t st, const void *d_buf, uint64_t buf_len, uint32_t 
     float ms = 0;
     rc = timed_launch(st, "CRC", &ms,
         [&] { return hipMemcpyAsync(dh.p, T.words.data(), T.words.size() * sizeof(unsigned long long), hipMemcpyHostToDevice, st); },
-        [&] { launch_crc(a, 1u << 22, st); },
+        [&] { launch_crc(a, kStrideBlocksWide, st); },
         [&] { return hipMemcpyAsync(crc_out, dout.p, nranges * sizeof(uint32_t), hipMemcpyDeviceToHost, st); });
     if (rc) return rc;
     Last &L = g_last.here();
@@ -96,9 +96,7 @@ int nlzm_hip_crc32_ranges(const uint8_t *buf, uint64_t buf_len, uint32_t nranges
     if (const int rc = host_stream(&st)) return rc;
     if ((!buf && buf_len) || (nranges && (!off || !len || !crc))) return fail(NLZM_HIP_E_ARG, "null argument");
     DevBuf d;
-    if (const int rc = d.alloc(buf_len)) return rc;
-    if (buf_len) HIPCHK(hipMemcpyAsync(d.p, buf, buf_len, hipMemcpyHostToDevice, st));
-    HIPCHK(hipStreamSynchronize(st));
+    if (const int rc = upload(d, buf, buf_len, st)) return rc;
     return nlzm_hip_crc32_ranges_dev(d.p, buf_len, nranges, off, len, crc);
 }
 
@@ -108,9 +106,7 @@ int nlzm_hip_crc32(const uint8_t *buf, uint64_t n, uint32_t seed, uint32_t *crc)
     if (const int rc = host_stream(&st)) return rc;
     if (!crc || (!buf && n)) return fail(NLZM_HIP_E_ARG, "null argument");
     DevBuf d;
-    if (const int rc = d.alloc(n)) return rc;
-    if (n) HIPCHK(hipMemcpyAsync(d.p, buf, n, hipMemcpyHostToDevice, st));
-    HIPCHK(hipStreamSynchronize(st));
+    if (const int rc = upload(d, buf, n, st)) return rc;
     return nlzm_hip_crc32_dev(d.p, n, seed, crc);
 }
 

@@ -7,6 +7,7 @@
 #include "nlzm_host_util.h"
 #include "nlzm_cut_host.h"
 #include "nlzm_cut.h"
+#include "nlzm_units.h"
 
 using namespace nlzm;
 
@@ -39,7 +40,7 @@ int cut_points_on(hipStream_t st, const void *d_src, uint64_t n, uint32_t avg_bi
     cut::Args a{};
     a.src = (const uint8_t *)d_src;
     a.n = n;
-    a.nsegs = n / cut::kSegment + (n % cut::kSegment ? 1 : 0);
+    a.nsegs = units::count(n, cut::kSegment);
     a.min_len = min_len; a.max_len = max_len;
     a.shift = 32 - avg_bits;
     a.cut_cap = n / min_len < cut_cap ? n / min_len : cut_cap;
@@ -54,7 +55,7 @@ int cut_points_on(hipStream_t st, const void *d_src, uint64_t n, uint32_t avg_bi
     float ms = 0;
     rc = timed_launch(st, "cut", &ms,
         [&] { return hipSuccess; },
-        [&] { launch_cut(a, 1u << 22, st); },
+        [&] { launch_cut(a, kStrideBlocksWide, st); },
         [&] { return hipMemcpyAsync(res, a.res, sizeof res, hipMemcpyDeviceToHost, st); });
     if (rc) return rc;
     L.us = 1000.0 * ms;
@@ -96,9 +97,7 @@ int nlzm_hip_cut_points(const uint8_t *src, uint64_t n, uint32_t avg_bits, uint6
     hipStream_t st;
     if (const int rc = host_stream(&st)) return rc;
     DevBuf d;
-    if (const int rc = d.alloc(n)) return rc;
-    if (n) HIPCHK(hipMemcpyAsync(d.p, src, n, hipMemcpyHostToDevice, st));
-    HIPCHK(hipStreamSynchronize(st));
+    if (const int rc = upload(d, src, n, st)) return rc;
     return cut_points_on(st, d.p, n, avg_bits, min_len, max_len, cut, cut_cap, ncuts);
 }
 

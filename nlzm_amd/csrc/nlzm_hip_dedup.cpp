@@ -28,8 +28,6 @@ PerDevice<Last> g_last;
 // the two options: the process's, like the library's error text (a multi-device call compresses no ranges)
 std::atomic<int64_t> g_dedup_ranges{ 0 }, g_hash_bits{ 64 };
 
-constexpr uint32_t kMaxBlocks = 1u << 20;           // workgroups of a launch at most: beyond them the waves stride
-
 // the arguments that need no device
 int check_args(uint64_t buf_len, uint32_t k, const uint64_t *off, const uint64_t *len, const uint32_t *first_of)
 {
@@ -39,8 +37,6 @@ int check_args(uint64_t buf_len, uint32_t k, const uint64_t *off, const uint64_t
     return 0;
 }
 
-using dedup::prefix_of;      // (nlzm_dedup_plan.h)
-
 // one round's pairs on the device: equal[p] for every pair
 int compare_pairs(hipStream_t st, const void *d_buf, const uint64_t *off, const uint64_t *len, const std::vector<dedup::IndexPair> &pairs, std::vector<uint8_t> &equal, double *us)
 {
@@ -48,7 +44,7 @@ int compare_pairs(hipStream_t st, const void *d_buf, const uint64_t *off, const 
     if (!np) return 0;
     std::vector<dedup::Pair> hp(np);
     for (size_t p = 0; p < np; p++) hp[p] = dedup::Pair{ off[pairs[p].rep], off[pairs[p].member], len[pairs[p].rep] };
-    const std::vector<unsigned long long> c0 = prefix_of((uint32_t)np, dedup::kChunk, [&](uint32_t p) { return hp[p].len; });
+    const std::vector<unsigned long long> c0 = units::prefix((uint32_t)np, dedup::kChunk, [&](uint32_t p) { return hp[p].len; });
     DevBuf dp, dc, dn, de;
     int rc = dp.alloc(np * sizeof(dedup::Pair));
     if (!rc) rc = dc.alloc((np + 1) * sizeof(unsigned long long));
@@ -63,7 +59,7 @@ int compare_pairs(hipStream_t st, const void *d_buf, const uint64_t *off, const 
             const hipError_t e = hipMemcpyAsync(dp.p, hp.data(), np * sizeof(dedup::Pair), hipMemcpyHostToDevice, st);
             return e != hipSuccess ? e : hipMemcpyAsync(dc.p, c0.data(), (np + 1) * sizeof(unsigned long long), hipMemcpyHostToDevice, st);
         },
-        [&] { launch_pairs(a, kMaxBlocks, st); },
+        [&] { launch_pairs(a, kStrideBlocks, st); },
         [&] { return hipMemcpyAsync(got.data(), de.p, np * sizeof(uint32_t), hipMemcpyDeviceToHost, st); });
     if (rc) return rc;
     *us += 1000.0 * ms;
@@ -80,7 +76,7 @@ int equal_ranges_on(hipStream_t st, const void *d_buf, uint32_t k, const uint64_
     uint64_t total = 0;
     for (uint32_t i = 0; i < k; i++) total += len[i];
     if (total && !d_buf) return fail(NLZM_HIP_E_ARG, "null argument");
-    const std::vector<unsigned long long> seg0 = prefix_of(k, dedup::kSegment, [&](uint32_t i) { return len[i]; });
+    const std::vector<unsigned long long> seg0 = units::prefix(k, dedup::kSegment, [&](uint32_t i) { return len[i]; });
     std::vector<unsigned long long> table(3 * (size_t)k + 1);      // off, len, seg0: one upload
     for (uint32_t i = 0; i < k; i++) { table[i] = off[i]; table[(size_t)k + i] = len[i]; }
     memcpy(table.data() + 2 * (size_t)k, seg0.data(), ((size_t)k + 1) * sizeof(unsigned long long));
@@ -95,7 +91,7 @@ int equal_ranges_on(hipStream_t st, const void *d_buf, uint32_t k, const uint64_
     float ms = 0;
     rc = timed_launch(st, "dedup fingerprints", &ms,
         [&] { return hipMemcpyAsync(dt.p, table.data(), table.size() * sizeof(unsigned long long), hipMemcpyHostToDevice, st); },
-        [&] { launch_fingerprints(a, kMaxBlocks, st); },
+        [&] { launch_fingerprints(a, kStrideBlocks, st); },
         [&] { return hipMemcpyAsync(fp.data(), df.p, (size_t)k * sizeof(uint64_t), hipMemcpyDeviceToHost, st); });
     if (rc) return rc;
     L.us += 1000.0 * ms;
@@ -159,25 +155,7 @@ int dedup_place(const uint8_t *d_from, uint8_t *d_to, uint32_t k, const uint64_t
     if (const int rc = host_stream(&st)) return rc;
     std::vector<range::Piece> hp;
     for (uint32_t i = 0; i < k; i++) if (len[i]) hp.push_back(range::Piece{ d_from + from[i], d_to + to[i], len[i] });
-    const size_t np = hp.size();
-    if (!np) return 0;
-    const std::vector<unsigned long long> c0 = prefix_of((uint32_t)np, range::kChunk, [&](uint32_t p) { return hp[p].len; });
-    DevBuf dp, dc;
-    int rc = dp.alloc(np * sizeof(range::Piece));
-    if (!rc) rc = dc.alloc((np + 1) * sizeof(unsigned long long));
-    if (rc) return rc;
-    const range::Args a{ dp.as<range::Piece>(), dc.as<unsigned long long>(), (uint32_t)np, c0[np] };
-    float ms = 0;
-    rc = timed_launch(st, "dedup gather", &ms,
-        [&] {
-            const hipError_t e = hipMemcpyAsync(dp.p, hp.data(), np * sizeof(range::Piece), hipMemcpyHostToDevice, st);
-            return e != hipSuccess ? e : hipMemcpyAsync(dc.p, c0.data(), (np + 1) * sizeof(unsigned long long), hipMemcpyHostToDevice, st);
-        },
-        [&] { launch_gather(a, kMaxBlocks, st); },
-        [] { return hipSuccess; });
-    if (rc) return rc;
-    g_last.here().gather_us += 1000.0 * ms;
-    return 0;
+    return gather_on(st, "dedup gather", hp, &g_last.here().gather_us);
 }
 
 }  // namespace nlzm
@@ -199,9 +177,7 @@ int nlzm_hip_equal_ranges(const uint8_t *buf, uint64_t buf_len, uint32_t k, cons
     hipStream_t st;
     if (const int rc = host_stream(&st)) return rc;
     DevBuf d;
-    if (const int rc = d.alloc(buf_len)) return rc;
-    if (buf_len) HIPCHK(hipMemcpyAsync(d.p, buf, buf_len, hipMemcpyHostToDevice, st));
-    HIPCHK(hipStreamSynchronize(st));
+    if (const int rc = upload(d, buf, buf_len, st)) return rc;
     return equal_ranges_on(st, d.p, k, off, len, first_of, fingerprint);
 }
 

@@ -21,8 +21,6 @@ namespace {
 struct Last { double us = 0; unsigned long long bytes = 0; };
 PerDevice<Last> g_last;
 
-constexpr uint32_t kMaxBlocks = 1u << 20;           // workgroups of a launch at most: beyond them the waves stride
-
 int check_args(const void *src, uint64_t src_len, const void *dst, uint64_t dst_len, uint32_t k, const uint64_t *src_off, const uint64_t *dst_off, const uint64_t *len,
                const uint8_t *elem)
 {
@@ -55,7 +53,7 @@ int planes_on(hipStream_t st, const void *d_src, void *d_dst, uint32_t k, const 
     float ms = 0;
     const int rc = timed_launch(st, "planes", &ms,
         [&] { return hipMemcpyAsync(dt.p, T.words.data(), T.words.size() * sizeof(unsigned long long), hipMemcpyHostToDevice, st); },
-        [&] { launch_planes(a, inverse, kMaxBlocks, st); },
+        [&] { launch_planes(a, inverse, kStrideBlocks, st); },
         [] { return hipSuccess; });
     if (rc) return rc;
     Last &L = g_last.here();
@@ -66,27 +64,12 @@ int planes_on(hipStream_t st, const void *d_src, void *d_dst, uint32_t k, const 
 
 void begin_call() { g_last.here() = Last{}; }
 
-// the ranges of a typed call against their buffer, and the element sizes: what needs no device
+// the ranges of a typed call against their buffer, the element sizes, and the scratch layout: what needs no device
 int check_typed(uint64_t n, uint32_t k, const uint64_t *off, const uint64_t *len, const uint8_t *elem, planes::Layout &lay)
 {
     char why[512] = "";
-    if (const int rc = planes::check_elems(k, elem, ErrText{ why, sizeof why })) return fail(rc, "%s", why);
-    if (!off || !len) return fail(NLZM_HIP_E_ARG, "null argument");
-    for (uint32_t i = 0; i < k; i++)
-        if (off[i] > n || len[i] > n - off[i])
-            return fail(NLZM_HIP_E_ARG, "range %u (offset %llu, %llu bytes) runs over the %llu bytes of the buffer", i, (unsigned long long)off[i], (unsigned long long)len[i],
-                        (unsigned long long)n);
+    if (const int rc = planes::check_typed_ranges(n, k, off, len, elem, ErrText{ why, sizeof why })) return fail(rc, "%s", why);
     if (const int rc = lay.make(k, len, planes::kPad, ErrText{ why, sizeof why })) return fail(rc, "%s", why);
-    return 0;
-}
-
-// a scratch allocation of the library's: NLZM_HIP_E_NOMEM when there is no room, and nothing is left open
-int scratch_alloc(DevBuf &b, uint64_t bytes, const char *what)
-{
-    if (hipMalloc(&b.p, bytes ? bytes : 16) != hipSuccess) {
-        (void)hipGetLastError(); b.p = nullptr;
-        return fail(NLZM_HIP_E_NOMEM, "no %llu bytes of device memory for %s", (unsigned long long)bytes, what);
-    }
     return 0;
 }
 
@@ -124,10 +107,8 @@ int nlzm_hip_planes(const uint8_t *src, uint64_t src_len, uint8_t *dst, uint64_t
     if (const int rc = host_stream(&st)) return rc;
     begin_call();
     DevBuf ds, dd;
-    if (const int rc = ds.alloc(src_len)) return rc;
     if (const int rc = dd.alloc(dst_len)) return rc;
-    if (src_len) HIPCHK(hipMemcpyAsync(ds.p, src, src_len, hipMemcpyHostToDevice, st));
-    HIPCHK(hipStreamSynchronize(st));
+    if (const int rc = upload(ds, src, src_len, st)) return rc;
     if (const int rc = planes_on(st, ds.p, dd.p, k, src_off, dst_off, len, elem, inverse != 0)) return rc;
     // only what the ranges wrote comes back: the bytes between them are the caller's
     for (const auto &r : planes::runs(k, dst_off, len)) HIPCHK(hipMemcpyAsync(dst + r.first, dd.as<uint8_t>() + r.first, r.second, hipMemcpyDeviceToHost, st));
@@ -148,7 +129,7 @@ int nlzm_hip_compress_ranges_typed_dev(const void *d_src, uint64_t n, uint32_t k
     if (dst_cap < bound) return fail(NLZM_HIP_E_CAPACITY, "dst_cap %llu, the ranges' streams may take %llu (nlzm_hip_compress_ranges_bound)", (unsigned long long)dst_cap, (unsigned long long)bound);
     begin_call();
     DevBuf scratch;
-    if (const int rc = scratch_alloc(scratch, lay.alloc, "the ranges' byte planes")) return rc;
+    if (const int rc = scratch.alloc_for(lay.alloc, "the ranges' byte planes")) return rc;
     HIPCHK(hipMemsetAsync(scratch.as<uint8_t>() + lay.total, 0, planes::kPad, st));
     if (const int rc = planes_on(st, d_src, scratch.p, k, off, lay.at.data(), len, elem, false)) return rc;
     return nlzm_hip_compress_ranges_dev(scratch.p, lay.total, k, lay.at.data(), len, hist_bits_req, d_dst, dst_cap, block_len, dst_len);
@@ -166,10 +147,8 @@ int nlzm_hip_compress_ranges_typed(const uint8_t *src, uint64_t n, uint32_t k, c
     const uint64_t bound = nlzm_hip_compress_ranges_bound(k, len);
     if (dst_cap < bound) return fail(NLZM_HIP_E_CAPACITY, "dst_cap %llu, the ranges' streams may take %llu (nlzm_hip_compress_ranges_bound)", (unsigned long long)dst_cap, (unsigned long long)bound);
     DevBuf in, out;
-    if (const int rc = in.alloc(n)) return rc;
-    if (const int rc = scratch_alloc(out, bound, "the ranges' streams")) return rc;
-    if (n) HIPCHK(hipMemcpyAsync(in.p, src, n, hipMemcpyHostToDevice, st));
-    HIPCHK(hipStreamSynchronize(st));
+    if (const int rc = out.alloc_for(bound, "the ranges' streams")) return rc;
+    if (const int rc = upload(in, src, n, st)) return rc;
     uint64_t got = 0;
     if (const int rc = nlzm_hip_compress_ranges_typed_dev(in.p, n, k, off, len, elem, hist_bits_req, out.p, bound, block_len, &got)) return rc;
     if (got) HIPCHK(hipMemcpy(dst, out.p, got, hipMemcpyDeviceToHost));
@@ -194,7 +173,7 @@ int nlzm_hip_decompress_blocks_typed_dev(const void *d_src, uint64_t src_len, ui
     if (const int rc = lay.make(nblocks, raw.data(), 0, ErrText{ why, sizeof why })) return fail(rc, "%s", why);
     if (lay.total > dst_cap) return fail(NLZM_HIP_E_CAPACITY, "the blocks decode to %llu bytes, dst_cap %llu", (unsigned long long)lay.total, (unsigned long long)dst_cap);
     DevBuf scratch;
-    if (const int rc = scratch_alloc(scratch, lay.total, "the blocks' byte planes")) return rc;
+    if (const int rc = scratch.alloc_for(lay.total, "the blocks' byte planes")) return rc;
     if (const int rc = nlzm_hip_decompress_blocks_dev(d_src, src_len, nblocks, block_len, raw.data(), scratch.p, lay.total, nullptr, &total)) return rc;
     begin_call();
     if (const int rc = planes_on(st, scratch.p, d_dst, nblocks, lay.at.data(), lay.at.data(), raw.data(), elem, true)) return rc;
@@ -217,16 +196,14 @@ int nlzm_hip_decompress_blocks_typed(const uint8_t *src, uint64_t src_len, uint3
     std::vector<uint64_t> boff, blen, raw(nblocks);
     if (const int rc = decode_split_host(src, src_len, nblocks, block_len, boff, blen)) return rc;
     DevBuf ds, dd;
-    if (const int rc = ds.alloc(src_len)) return rc;
-    HIPCHK(hipMemcpyAsync(ds.p, src, src_len, hipMemcpyHostToDevice, st));
-    HIPCHK(hipStreamSynchronize(st));
+    if (const int rc = upload(ds, src, src_len, st)) return rc;
     uint64_t total = 0;
     if (raw_len) memcpy(raw.data(), raw_len, (size_t)nblocks * sizeof(uint64_t));
     else if (const int rc = nlzm_hip_decompress_blocks_dev(ds.p, src_len, nblocks, blen.data(), nullptr, nullptr, 0, raw.data(), &total)) return rc;
     planes::Layout lay;
     if (const int rc = lay.make(nblocks, raw.data(), 0, ErrText{ why, sizeof why })) return fail(rc, "%s", why);
     if (lay.total > dst_cap) return fail(NLZM_HIP_E_CAPACITY, "the blocks decode to %llu bytes, dst_cap %llu", (unsigned long long)lay.total, (unsigned long long)dst_cap);
-    if (const int rc = scratch_alloc(dd, lay.total, "the decoded blocks")) return rc;
+    if (const int rc = dd.alloc_for(lay.total, "the decoded blocks")) return rc;
     if (const int rc = nlzm_hip_decompress_blocks_typed_dev(ds.p, src_len, nblocks, blen.data(), raw.data(), elem, dd.p, lay.total, nullptr, &total)) return rc;
     if (total) HIPCHK(hipMemcpy(dst, dd.p, total, hipMemcpyDeviceToHost));
     if (raw_len_out) memcpy(raw_len_out, raw.data(), (size_t)nblocks * sizeof(uint64_t));

@@ -36,12 +36,7 @@ int execute(hipStream_t st, const Plan &P, uint32_t nblocks, const std::vector<c
 {
     Last &L = g_last.here();
     DevBuf scratch;
-    if (P.scratch) {
-        if (hipMalloc(&scratch.p, P.scratch) != hipSuccess) {
-            (void)hipGetLastError(); scratch.p = nullptr;
-            return fail(NLZM_HIP_E_NOMEM, "no %llu bytes of device memory for the blocks that are read in part", (unsigned long long)P.scratch);
-        }
-    }
+    if (P.scratch) if (const int rc = scratch.alloc_for(P.scratch, "the blocks that are read in part")) return rc;
     std::vector<dec::StreamArgs> args;
     std::vector<uint32_t> block_of;
     for (uint32_t b = 0; b < nblocks; b++) {
@@ -71,25 +66,8 @@ int execute(hipStream_t st, const Plan &P, uint32_t nblocks, const std::vector<c
     // the gather launch: every piece that lies in the scratch buffer, on the same stream behind the decode
     std::vector<range::Piece> hp;
     std::vector<unsigned long long> c0;
-    const unsigned long long nchunks = range::pack_pieces(P.pieces, scratch.as<uint8_t>(), d_dst, range::kChunk, hp, c0);
-    if (const size_t np = hp.size()) {
-        if (np > 0xFFFFFFFFull) return fail(NLZM_HIP_E_ARG, "more than 2^32 pieces in one call");
-        DevBuf dp, dc;
-        int rc = dp.alloc(np * sizeof(range::Piece));
-        if (!rc) rc = dc.alloc((np + 1) * sizeof(unsigned long long));
-        if (rc) return rc;
-        const range::Args a{ dp.as<range::Piece>(), dc.as<unsigned long long>(), (uint32_t)np, nchunks };
-        float ms = 0;
-        rc = timed_launch(st, "gather", &ms,
-            [&] {
-                const hipError_t e = hipMemcpyAsync(dp.p, hp.data(), np * sizeof(range::Piece), hipMemcpyHostToDevice, st);
-                return e != hipSuccess ? e : hipMemcpyAsync(dc.p, c0.data(), (np + 1) * sizeof(unsigned long long), hipMemcpyHostToDevice, st);
-            },
-            [&] { launch_gather(a, 1u << 20, st); },
-            [] { return hipSuccess; });
-        if (rc) return rc;
-        L.gather_us += 1000.0 * ms;
-    }
+    range::pack_pieces(P.pieces, scratch.as<uint8_t>(), d_dst, range::kChunk, hp, c0);     // (c0: gather_on makes its own, from the same units::count)
+    if (const int rc = gather_on(st, "gather", hp, &L.gather_us)) return rc;
     if (first_bad) *first_bad = nblocks;
     if (crc) {
         // the blocks this call decoded in full, hashed where they lie: in the destination (direct) or in the scratch buffer
@@ -129,6 +107,31 @@ int enter(hipStream_t *st, const void *src, uint32_t nblocks, uint32_t nranges, 
 }  // namespace
 
 namespace nlzm {
+
+int gather_on(hipStream_t st, const char *what, const std::vector<range::Piece> &pieces, double *us)
+{
+    const size_t np = pieces.size();
+    if (!np) return 0;
+    if (np > 0xFFFFFFFFull) return fail(NLZM_HIP_E_ARG, "more than 2^32 pieces in one call");
+    const std::vector<unsigned long long> c0 = units::prefix((uint32_t)np, range::kChunk, [&](uint32_t p) { return pieces[p].len; });
+    DevBuf dp, dc;
+    int rc = dp.alloc(np * sizeof(range::Piece));
+    if (!rc) rc = dc.alloc((np + 1) * sizeof(unsigned long long));
+    if (rc) return rc;
+    const range::Args a{ dp.as<range::Piece>(), dc.as<unsigned long long>(), (uint32_t)np, c0[np] };
+    float ms = 0;
+    rc = timed_launch(st, what, &ms,
+        [&] {
+            const hipError_t e = hipMemcpyAsync(dp.p, pieces.data(), np * sizeof(range::Piece), hipMemcpyHostToDevice, st);
+            return e != hipSuccess ? e : hipMemcpyAsync(dc.p, c0.data(), (np + 1) * sizeof(unsigned long long), hipMemcpyHostToDevice, st);
+        },
+        [&] { launch_gather(a, kStrideBlocks, st); },
+        [] { return hipSuccess; });
+    if (rc) return rc;
+    *us += 1000.0 * ms;
+    return 0;
+}
+
 int range_counter(const char *key, uint64_t *value)
 {
     const Last &L = g_last.here();
@@ -144,6 +147,7 @@ int range_counter(const char *key, uint64_t *value)
     if (!strcmp(key, "range_chunk_bytes")) { *value = range::kChunk; return 0; }
     return fail(NLZM_HIP_E_ARG, "unknown counter %s", key);
 }
+
 }  // namespace nlzm
 
 extern "C" {

@@ -19,7 +19,7 @@
 namespace nlzm {
 namespace dec { struct StreamArgs; struct StreamResult; }
 namespace crc { struct Args; }
-namespace range { struct Args; }
+namespace range { struct Args; struct Piece; }
 
 // nlzm_hip.cpp: the library's error text (what fail and HIPCHK end in) and its stream (an error if nlzm_hip_init has not succeeded)
 int host_error(int code, const char *text);
@@ -34,6 +34,8 @@ void launch_split(const void *d_src, unsigned long long len, uint32_t nblocks, u
 void launch_compare(const void *d_a, const void *d_b, unsigned long long n, unsigned long long *d_first, hipStream_t st);
 void launch_crc(const crc::Args &a, uint32_t max_blocks, hipStream_t st);
 void launch_gather(const range::Args &a, uint32_t max_blocks, hipStream_t st);
+// nlzm_hip_range.cpp: ONE gather launch for the non-empty pieces (no piece, no launch), its tables uploaded and its device time ADDED to *us
+int gather_on(hipStream_t st, const char *what, const std::vector<range::Piece> &pieces, double *us);
 // nlzm_hip_decode.cpp
 void decode_begin_call();                           // a new call: its device time and pass count start at 0
 double decode_call_ms();                            // device time of the call's passes so far
@@ -67,12 +69,31 @@ inline int fail(int code, const char *fmt, ...)
             return fail(e_ == hipErrorOutOfMemory ? NLZM_HIP_E_NOMEM : NLZM_HIP_E_NODEVICE, "%s failed: %s", #expr, hipGetErrorString(e_)); \
     } while (0)
 
+// workgroups of a launch at most, beyond them the waves stride (nlzm_units.h): the launches of four waves a workgroup, and the CRC's and the cut
+// points' (as they were first set; nobody has measured another value of either)
+constexpr uint32_t kStrideBlocks = 1u << 20, kStrideBlocksWide = 1u << 22;
+
 struct DevBuf {
     void *p = nullptr;
     ~DevBuf() { if (p) (void)hipFree(p); }
     int alloc(size_t bytes) { HIPCHK(hipMalloc(&p, bytes ? bytes : 16)); return 0; }
+    // a scratch allocation of a size the caller's arguments decide: NLZM_HIP_E_NOMEM when there is no room, and nothing is left open
+    int alloc_for(uint64_t bytes, const char *what)
+    {
+        if (hipMalloc(&p, bytes ? bytes : 16) == hipSuccess) return 0;
+        (void)hipGetLastError(); p = nullptr;
+        return fail(NLZM_HIP_E_NOMEM, "no %llu bytes of device memory for %s", (unsigned long long)bytes, what);
+    }
     template <class T> T *as() const { return (T *)p; }
 };
+// a host buffer onto the device: d allocated, the n bytes at src copied (n = 0: none), the stream synchronised
+inline int upload(DevBuf &d, const void *src, uint64_t n, hipStream_t st)
+{
+    if (const int rc = d.alloc(n)) return rc;
+    if (n) HIPCHK(hipMemcpyAsync(d.p, src, n, hipMemcpyHostToDevice, st));
+    HIPCHK(hipStreamSynchronize(st));
+    return 0;
+}
 struct Events {
     hipEvent_t ev[2] = { nullptr, nullptr };
     ~Events() { for (auto &e : ev) if (e) (void)hipEventDestroy(e); }

@@ -26,6 +26,7 @@
 
 #include "xw.h"
 #include "nlzm_range.h"
+#include "nlzm_units.h"
 
 namespace nlzm {
 namespace planes {
@@ -160,8 +161,7 @@ XW_FN void planes_role(const Args &a, bool inverse, unsigned long long w, unsign
     uint8_t *image = xw::lds<Lds>()->image + (size_t)xw::wave() * kImage;
     const uint32_t l = xw::lane();
     for (unsigned long long g = w; g < a.nsegs; g += nwaves) {
-        uint32_t lo = 0, hi = a.k;                  // the range whose segments hold g: the last r with seg0[r] <= g (empty ranges own none)
-        while (hi - lo > 1) { const uint32_t mid = lo + (hi - lo) / 2; if (a.seg0[mid] <= g) lo = mid; else hi = mid; }
+        const uint32_t lo = units::owner_of(a.seg0, a.k, g);               // the range whose segments hold g
         const unsigned long long n = a.len[lo], e = a.elem[lo], m = n / e, whole = m * e, at = (g - a.seg0[lo]) * kSegment;
         const unsigned long long left = whole > at ? whole - at : 0;
         const uint32_t body = (uint32_t)(left < kSegment ? left : kSegment);

@@ -20,36 +20,33 @@ static_assert(sizeof(g_planes_lds) == planes::lds_bytes(kPlanesThreads / 64), "o
 
 __device__ __forceinline__ planes::Args global_args(planes::Args a)       // (pointers handed over in a struct: global ones, not flat)
 {
-    a.src = NLZM_RANGE_G(const uint8_t, a.src);
-    a.dst = NLZM_RANGE_G(uint8_t, a.dst);
-    a.src_off = NLZM_RANGE_G(const unsigned long long, a.src_off);
-    a.dst_off = NLZM_RANGE_G(const unsigned long long, a.dst_off);
-    a.len = NLZM_RANGE_G(const unsigned long long, a.len);
-    a.elem = NLZM_RANGE_G(const unsigned long long, a.elem);
-    a.seg0 = NLZM_RANGE_G(const unsigned long long, a.seg0);
+    a.src = NLZM_GLOBAL(const uint8_t, a.src);
+    a.dst = NLZM_GLOBAL(uint8_t, a.dst);
+    a.src_off = NLZM_GLOBAL(const unsigned long long, a.src_off);
+    a.dst_off = NLZM_GLOBAL(const unsigned long long, a.dst_off);
+    a.len = NLZM_GLOBAL(const unsigned long long, a.len);
+    a.elem = NLZM_GLOBAL(const unsigned long long, a.elem);
+    a.seg0 = NLZM_GLOBAL(const unsigned long long, a.seg0);
     return a;
 }
 
 __global__ __launch_bounds__(kPlanesThreads) void planes_forward_kernel(planes::Args args)
 {
     const planes::Args a = global_args(args);
-    constexpr uint32_t wpb = kPlanesThreads / 64;
-    planes::planes_role(a, false, (unsigned long long)blockIdx.x * wpb + xw::wave(), (unsigned long long)gridDim.x * wpb);
+    planes::planes_role(a, false, units::wave<kPlanesThreads>(), units::waves<kPlanesThreads>());
 }
 
 __global__ __launch_bounds__(kPlanesThreads) void planes_inverse_kernel(planes::Args args)
 {
     const planes::Args a = global_args(args);
-    constexpr uint32_t wpb = kPlanesThreads / 64;
-    planes::planes_role(a, true, (unsigned long long)blockIdx.x * wpb + xw::wave(), (unsigned long long)gridDim.x * wpb);
+    planes::planes_role(a, true, units::wave<kPlanesThreads>(), units::waves<kPlanesThreads>());
 }
 
 // ONE launch for all ranges of a call; no segment, no launch
 void launch_planes(const planes::Args &a, bool inverse, uint32_t max_blocks, hipStream_t st)
 {
     if (!a.nsegs) return;
-    const unsigned long long want = (a.nsegs + kPlanesThreads / 64 - 1) / (kPlanesThreads / 64);
-    const dim3 grid((uint32_t)(want < max_blocks ? want : max_blocks));
+    const dim3 grid = units::grid<kPlanesThreads>(a.nsegs, max_blocks);
     if (inverse) hipLaunchKernelGGL(planes_inverse_kernel, grid, dim3(kPlanesThreads), 0, st, a);
     else hipLaunchKernelGGL(planes_forward_kernel, grid, dim3(kPlanesThreads), 0, st, a);
 }

@@ -5,6 +5,7 @@
 //   planes::check_ranges   ... and every range against both buffers (len > src_len - src_off, len > dst_len - dst_off: NLZM_HIP_E_ARG, named), the
 //                          destinations against each other -- sorted by dst_off, empty ones left out, a range that starts before the one in front of it
 //                          ends overlaps it: NLZM_HIP_E_ARG, both named -- and the two buffers against each other (there is no in-place form)
+//   planes::check_typed_ranges   k, the element sizes and every range of a typed call against its one buffer (check_in_buffer, nlzm_read_plan.h)
 //   planes::Table          the launch's arguments (planes::Args, nlzm_planes.h): src_off, dst_off, len, elem of every range and seg0, k + 1 entries --
 //                          range r owns segments [seg0[r], seg0[r + 1]) of `segment` bytes --, one array, one upload
 //   planes::runs           the destinations as sorted runs of bytes that lie back to back: what a host-buffer call copies back
@@ -69,6 +70,15 @@ inline int check_ranges(uint64_t src_at, uint64_t src_len, uint64_t dst_at, uint
     return 0;
 }
 
+// the ranges of a typed call against the n bytes of their buffer, and the element sizes
+inline int check_typed_ranges(uint64_t n, uint32_t k, const uint64_t *off, const uint64_t *len, const uint8_t *elem, ErrText err)
+{
+    if (const int rc = check_elems(k, elem, err)) return rc;
+    if (!off || !len) return plan_error(err, NLZM_HIP_E_ARG, "null argument");
+    for (uint32_t i = 0; i < k; i++) if (const int rc = check_in_buffer(i, off[i], len[i], n, err)) return rc;
+    return 0;
+}
+
 // the destinations of checked ranges as runs (offset, bytes), ascending: ranges that lie back to back are one run
 inline std::vector<std::pair<uint64_t, uint64_t>> runs(uint32_t k, const uint64_t *dst_off, const uint64_t *len)
 {
@@ -102,7 +112,7 @@ struct Table {
         unsigned long long *w = words.data();
         for (uint32_t i = 0; i < n; i++) {
             w[i] = src_off[i]; w[(size_t)n + i] = dst_off[i]; w[2 * (size_t)n + i] = len[i]; w[3 * (size_t)n + i] = elem[i]; w[4 * (size_t)n + i] = nsegs;
-            nsegs += len[i] / segment + (len[i] % segment ? 1 : 0);
+            nsegs += units::count(len[i], segment);
             bytes += len[i];                        // (ranges inside a buffer whose destinations do not overlap: below 2^64)
             if (nsegs > (1ull << 40)) return plan_error(err, NLZM_HIP_E_ARG, "the ranges of one call may hold 2^40 segments of %llu bytes in all", segment);
         }

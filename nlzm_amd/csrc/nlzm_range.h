@@ -16,12 +16,7 @@
 #pragma once
 
 #include "xw.h"
-
-#ifndef NLZM_SIM
-#define NLZM_RANGE_G(T, x) ((T *)(__attribute__((address_space(1))) T *)(unsigned long long)(x))     // (pointers read from memory: global ones, not flat)
-#else
-#define NLZM_RANGE_G(T, x) ((T *)(x))
-#endif
+#include "nlzm_units.h"
 
 namespace nlzm {
 namespace range {
@@ -73,11 +68,10 @@ XW_FN void copy_chunk(const uint8_t *s, uint8_t *d, unsigned long long n)
 XW_FN void gather_role(const Args &a, unsigned long long w, unsigned long long nwaves)
 {
     for (unsigned long long g = w; g < a.nchunks; g += nwaves) {
-        uint32_t lo = 0, hi = a.npieces;            // the piece whose chunks hold g: the last p with chunk0[p] <= g (empty pieces own none)
-        while (hi - lo > 1) { const uint32_t m = lo + (hi - lo) / 2; if (a.chunk0[m] <= g) lo = m; else hi = m; }
+        const uint32_t lo = units::owner_of(a.chunk0, a.npieces, g);       // the piece whose chunks hold g
         const Piece p = a.pieces[lo];
         const unsigned long long at = (g - a.chunk0[lo]) * kChunk, left = p.len - at;
-        copy_chunk(NLZM_RANGE_G(const uint8_t, p.src) + at, NLZM_RANGE_G(uint8_t, p.dst) + at, left < kChunk ? left : kChunk);
+        copy_chunk(NLZM_GLOBAL(const uint8_t, p.src) + at, NLZM_GLOBAL(uint8_t, p.dst) + at, left < kChunk ? left : kChunk);
     }
 }
 

@@ -12,18 +12,16 @@ constexpr uint32_t kGatherThreads = 256;
 __global__ __launch_bounds__(kGatherThreads) void range_gather_kernel(range::Args args)
 {
     range::Args a = args;
-    a.pieces = NLZM_RANGE_G(const range::Piece, a.pieces);
-    a.chunk0 = NLZM_RANGE_G(const unsigned long long, a.chunk0);
-    constexpr uint32_t wpb = kGatherThreads / 64;
-    range::gather_role(a, (unsigned long long)blockIdx.x * wpb + xw::wave(), (unsigned long long)gridDim.x * wpb);
+    a.pieces = NLZM_GLOBAL(const range::Piece, a.pieces);
+    a.chunk0 = NLZM_GLOBAL(const unsigned long long, a.chunk0);
+    range::gather_role(a, units::wave<kGatherThreads>(), units::waves<kGatherThreads>());
 }
 
 // ONE launch for all pieces of a call; no chunk, no launch
 void launch_gather(const range::Args &a, uint32_t max_blocks, hipStream_t st)
 {
     if (!a.nchunks) return;
-    const unsigned long long want = (a.nchunks + kGatherThreads / 64 - 1) / (kGatherThreads / 64);
-    hipLaunchKernelGGL(range_gather_kernel, dim3((uint32_t)(want < max_blocks ? want : max_blocks)), dim3(kGatherThreads), 0, st, a);
+    hipLaunchKernelGGL(range_gather_kernel, units::grid<kGatherThreads>(a.nchunks, max_blocks), dim3(kGatherThreads), 0, st, a);
 }
 
 }  // namespace nlzm

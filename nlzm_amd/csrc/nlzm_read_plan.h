@@ -4,7 +4,8 @@
 //   equal_shares       the raw lengths of the blocks of a container made from n bytes (nlzm_hip_verify*)
 //   range::make_plan   which bytes of which block a set of ranges needs, where each block is decoded to, which piece goes where
 //   range::for_each_part   the walk both of its loops and the command line's slicing make: the non-empty blocks a range intersects
-//   range::pack_pieces the gather launch's arguments: the non-empty pieces and their chunk prefix table
+//   check_in_buffer    a range against the bytes of its buffer: the one text of that refusal
+//   range::pack_pieces the gather launch's arguments: the non-empty pieces and their chunk prefix table (nlzm_units.h)
 //   crc::SegTable      the CRC launch's arguments: off / len / seg0 of the ranges, checked against the buffer
 // (the split of a host buffer into block streams by their frame headers sits beside stream_length: nlzm_host_decode.h, split_streams.)
 // Standard library only; compiles with plain g++ -std=c++17.  An error leaves as an NLZM_HIP_E_* code and its text in the caller's buffer.
@@ -19,6 +20,7 @@
 #include <vector>
 
 #include "../../include/nlzm_hip.h"
+#include "nlzm_units.h"
 
 namespace nlzm {
 
@@ -30,6 +32,14 @@ inline int plan_error(ErrText e, int code, const char *fmt, ...)
     if (e.text && e.cap) vsnprintf(e.text, e.cap, fmt, ap);
     va_end(ap);
     return code;
+}
+
+// Range i, len bytes from off, against the buf_len bytes of its buffer (no off + len: it can wrap)
+inline int check_in_buffer(uint32_t i, uint64_t off, uint64_t len, uint64_t buf_len, ErrText err)
+{
+    if (off <= buf_len && len <= buf_len - off) return 0;
+    return plan_error(err, NLZM_HIP_E_ARG, "range %u (offset %llu, %llu bytes) runs over the %llu bytes of the buffer", i, (unsigned long long)off, (unsigned long long)len,
+                      (unsigned long long)buf_len);
 }
 
 // The blocks of a container made from n bytes hold ceil(n / nblocks) bytes each, the last ones fewer
@@ -129,7 +139,7 @@ inline unsigned long long pack_pieces(const std::vector<PlanPiece> &pieces, cons
         if (!p.len) continue;
         out.push_back(Piece{ scratch + p.scratch_off, dst + p.dst_off, p.len });
         chunk0.push_back(nchunks);
-        nchunks += (p.len + chunk - 1) / chunk;
+        nchunks += units::count(p.len, chunk);
     }
     chunk0.push_back(nchunks);
     return nchunks;
@@ -158,11 +168,9 @@ struct SegTable {
         words.assign(3 * ((size_t)n + 1), 0);
         unsigned long long *h_off = words.data(), *h_len = h_off + n + 1, *h_seg0 = h_len + n + 1;
         for (uint32_t i = 0; i < n; i++) {
-            if (range_off[i] > buf_len || range_len[i] > buf_len - range_off[i])      // (no off + len: it can wrap)
-                return plan_error(err, NLZM_HIP_E_ARG, "range %u (offset %llu, %llu bytes) runs over the %llu bytes of the buffer", i, (unsigned long long)range_off[i],
-                                  (unsigned long long)range_len[i], (unsigned long long)buf_len);
+            if (const int rc = check_in_buffer(i, range_off[i], range_len[i], buf_len, err)) return rc;
             h_off[i] = range_off[i]; h_len[i] = range_len[i]; h_seg0[i] = nsegs;
-            nsegs += range_len[i] / segment + (range_len[i] % segment ? 1 : 0);
+            nsegs += units::count(range_len[i], segment);
             bytes += range_len[i];
             if (nsegs > (1ull << 31)) return plan_error(err, NLZM_HIP_E_ARG, "the ranges of one call may hold 2^31 segments of %llu bytes in all", segment);
         }

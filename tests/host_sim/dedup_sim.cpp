@@ -57,19 +57,11 @@ constexpr unsigned long long kCanary64 = 0xC0FFEE1122334455ull, kUnwritten64 = 0
 
 void die(const char *what) { fprintf(stderr, "dedup_sim: %s\n", what); exit(3); }
 
-template <class Len>
-std::vector<unsigned long long> prefix_of(size_t n, unsigned long long unit, Len len)
-{
-    std::vector<unsigned long long> t(n + 1, 0);
-    for (size_t i = 0; i < n; i++) t[i + 1] = t[i] + len(i) / unit + (len(i) % unit ? 1 : 0);
-    return t;
-}
-
 // the fingerprints of the ranges of the bytes at buf, as the library's host side launches them
 std::vector<unsigned long long> fingerprints(const uint8_t *buf, const std::vector<unsigned long long> &off, const std::vector<unsigned long long> &len, uint32_t threads, uint32_t blocks)
 {
     const size_t k = off.size();
-    const std::vector<unsigned long long> seg0 = prefix_of(k, dedup::kSegment, [&](size_t i) { return len[i]; });
+    const std::vector<unsigned long long> seg0 = units::prefix((uint32_t)k, dedup::kSegment, [&](uint32_t i) { return len[i]; });      // (the library's: nlzm_units.h)
     std::vector<unsigned long long> seg_h(seg0[k] + 1, kUnwritten64), fp(k + 1, kUnwritten64);
     seg_h[seg0[k]] = kCanary64; fp[k] = kCanary64;
     Launch L{ kFingerprint, dedup::FpArgs{ buf, off.data(), len.data(), seg0.data(), seg_h.data(), fp.data(), (uint32_t)k, seg0[k] }, dedup::PairArgs{}, threads };
@@ -86,7 +78,7 @@ std::vector<unsigned long long> fingerprints(const uint8_t *buf, const std::vect
 std::vector<uint32_t> verdicts(const uint8_t *buf, const std::vector<dedup::Pair> &pairs, uint32_t threads, uint32_t blocks)
 {
     const size_t np = pairs.size();
-    const std::vector<unsigned long long> c0 = prefix_of(np, dedup::kChunk, [&](size_t p) { return pairs[p].len; });
+    const std::vector<unsigned long long> c0 = units::prefix((uint32_t)np, dedup::kChunk, [&](uint32_t p) { return pairs[p].len; });
     std::vector<uint32_t> ne(c0[np] + 1, kUnwritten32), eq(np + 1, kUnwritten32);
     ne[c0[np]] = kCanary32; eq[np] = kCanary32;
     Launch L{ kPair, dedup::FpArgs{}, dedup::PairArgs{ buf, pairs.data(), c0.data(), ne.data(), eq.data(), (uint32_t)np, c0[np] }, threads };

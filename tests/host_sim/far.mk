@@ -2,7 +2,7 @@
 # lane a fiber (xw_sim.cpp), under UBSan as dedup_sim_san is (AddressSanitizer does not follow the fibers' hand-switched stacks).  TEST HARNESS ONLY.
 CSRC = ../../nlzm_amd/csrc
 SRC  = far_sim.cpp xw_sim.cpp
-DEPS = $(SRC) $(CSRC)/nlzm_crc.h $(CSRC)/nlzm_dedup.h $(CSRC)/nlzm_planes.h $(CSRC)/nlzm_range.h $(CSRC)/nlzm_dedup_plan.h $(CSRC)/nlzm_planes_plan.h $(CSRC)/nlzm_read_plan.h $(CSRC)/xw.h
+DEPS = $(SRC) $(CSRC)/nlzm_crc.h $(CSRC)/nlzm_dedup.h $(CSRC)/nlzm_planes.h $(CSRC)/nlzm_range.h $(CSRC)/nlzm_dedup_plan.h $(CSRC)/nlzm_planes_plan.h $(CSRC)/nlzm_read_plan.h $(CSRC)/nlzm_units.h $(CSRC)/xw.h
 CXXFLAGS = -O2 -g -std=c++17 -Wall -Wno-unknown-pragmas -Wno-unused-function
 all: far_sim_san
 far_sim_san: $(DEPS)

@@ -1,6 +1,6 @@
 // far_plan_sim.cpp -- the host tables of the range entry points for lengths nobody can allocate: crc::SegTable (nlzm_read_plan.h), planes::check_ranges,
-// planes::Table and planes::Layout (nlzm_planes_plan.h), container::make_ranges_plan (nlzm_container_plan.h), dedup::check_ranges and dedup::prefix_of
-// (nlzm_dedup_plan.h) -- the headers the library includes -- in a program of its own, under AddressSanitizer and UBSan.  TEST HARNESS ONLY
+// planes::Table and planes::Layout (nlzm_planes_plan.h), container::make_ranges_plan (nlzm_container_plan.h), dedup::check_ranges (nlzm_dedup_plan.h)
+// and units::prefix (nlzm_units.h) -- the headers the library includes -- in a program of its own, under AddressSanitizer and UBSan.  TEST HARNESS ONLY
 // (tests/test_far_plan.py, which holds the expected values: Python's integers).
 //
 //   far_plan_sim <cases>     every case: "T <buf_len> <crc_segment> <planes_segment> <dedup_segment> <k> <off> <len> ... (k pairs)".  Four lines a case:
@@ -83,7 +83,7 @@ int main(int argc, char **argv)
         if (const int rc3 = dedup::check_ranges(buf_len, k, off.data(), len.data(), err)) printf("dedup error %d %s\n", rc3, text);
         else {
             printf("dedup");
-            for (unsigned long long v : dedup::prefix_of(k, dedup_seg, [&](uint32_t i) { return len[i]; })) printf(" %llu", v);
+            for (unsigned long long v : units::prefix(k, dedup_seg, [&](uint32_t i) { return len[i]; })) printf(" %llu", v);
             printf("\n");
         }
     }

@@ -9,7 +9,7 @@
 //       I <off> <len> <at>                       the <len> bytes of the file <islands> from <at> on, to offset <off> of the source
 //       C <k> <off> <len> ...                    the CRC32s of k ranges, one launch of the segments role and one of the combine role, from the table the
 //                                                library's host side makes (crc::SegTable)
-//       F <k> <off> <len> ...                    the fingerprints of k ranges, one launch of each role, from dedup::prefix_of's table
+//       F <k> <off> <len> ...                    the fingerprints of k ranges, one launch of each role, from units::prefix's table
 //       Q <k> <a> <b> <len> ...                  the verdicts of k pairs of offsets
 //       P <inverse> <k> <src_off> <dst_off> <len> <e> ...
 //                                                one launch of the planes role into the destination buffer; prints the CRC32 of every destination, checks
@@ -153,7 +153,7 @@ int main(int argc, char **argv)
             if (fscanf(f, "%u", &k) != 1 || !k || !read_ranges(f, n, k, off, len)) return 2;
             if (dedup::check_ranges(n, k, off.data(), len.data(), ErrText{ why, sizeof why })) { fprintf(stderr, "far_sim: %s\n", why); return 2; }
             std::vector<unsigned long long> o(off.begin(), off.end()), l(len.begin(), len.end());
-            const std::vector<unsigned long long> seg0 = dedup::prefix_of(k, dedup::kSegment, [&](uint32_t i) { return l[i]; });
+            const std::vector<unsigned long long> seg0 = units::prefix(k, dedup::kSegment, [&](uint32_t i) { return l[i]; });
             std::vector<unsigned long long> seg_h(seg0[k] + 1, 0xDEADBEEFDEADBEEFull), fp(k + 1, 0xDEADBEEFDEADBEEFull);
             seg_h[seg0[k]] = kCanary64; fp[k] = kCanary64;
             Launch L{};
@@ -166,7 +166,7 @@ int main(int argc, char **argv)
             if (fscanf(f, "%u", &k) != 1 || !k || k > 65536) return 2;
             std::vector<dedup::Pair> pairs(k);
             for (auto &p : pairs) if (fscanf(f, "%llu %llu %llu", &p.a, &p.b, &p.len) != 3 || p.a > n || p.b > n || p.len > n - p.a || p.len > n - p.b) return 2;
-            const std::vector<unsigned long long> c0 = dedup::prefix_of(k, dedup::kChunk, [&](uint32_t p) { return pairs[p].len; });
+            const std::vector<unsigned long long> c0 = units::prefix(k, dedup::kChunk, [&](uint32_t p) { return pairs[p].len; });
             std::vector<uint32_t> ne(c0[k] + 1, 0xDEADBEEFu), eq(k + 1, 0xDEADBEEFu);
             ne[c0[k]] = kCanary32; eq[k] = kCanary32;
             Launch L{};

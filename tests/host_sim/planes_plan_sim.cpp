@@ -95,6 +95,12 @@ int sweep()
         planes::Layout L;
         if (L.make(2, huge, 128, err) != NLZM_HIP_E_ARG || L.make(2, huge, 0, err) != NLZM_HIP_E_ARG) die("a sum that wraps");
         if (planes::check_ranges(0, 100, 4096, 100, 2, wrap_off, z.data(), two, e2, err) != NLZM_HIP_E_ARG || !strstr(why, "range 0 ")) die("an offset that wraps");
+        // the typed calls' check: one buffer, the ranges may overlap
+        const uint64_t in_off[2] = { 98, 0 }, over_off[2] = { 0, 99 };
+        if (planes::check_typed_ranges(100, 2, in_off, two, e2, err) != 0) die("typed ranges inside their buffer");
+        if (planes::check_typed_ranges(100, 2, over_off, two, e2, err) != NLZM_HIP_E_ARG || !strstr(why, "range 1 (offset 99, 2 bytes) runs over the 100 bytes of the buffer")) die("a typed range over its buffer's end");
+        if (planes::check_typed_ranges(100, 2, wrap_off, two, e2, err) != NLZM_HIP_E_ARG || !strstr(why, "range 0 ")) die("a typed offset that wraps");
+        if (planes::check_typed_ranges(100, 2, in_off, two, nullptr, err) != NLZM_HIP_E_ARG || planes::check_typed_ranges(100, 2, nullptr, two, e2, err) != NLZM_HIP_E_ARG) die("typed: null");
     }
     printf("sweep: cases=%llu refused=%llu\n", cases, refused);
     return 0;

@@ -1,6 +1,6 @@
 """CPU suite: the host tables of the range entry points for lengths nobody can allocate -- crc::SegTable (nlzm_read_plan.h), planes::check_ranges,
-planes::Table and planes::Layout (nlzm_planes_plan.h), container::make_ranges_plan (nlzm_container_plan.h), dedup::check_ranges and dedup::prefix_of
-(nlzm_dedup_plan.h).  The harness (tests/host_sim/far_plan_sim.cpp) is a program of its own under AddressSanitizer and UBSan and includes the
+planes::Table and planes::Layout (nlzm_planes_plan.h), container::make_ranges_plan (nlzm_container_plan.h), dedup::check_ranges (nlzm_dedup_plan.h)
+and units::prefix (nlzm_units.h).  The harness (tests/host_sim/far_plan_sim.cpp) is a program of its own under AddressSanitizer and UBSan and includes the
 headers the library includes; every number it prints is held to Python's integers: ranges of 2^32 - 1, 2^32, 2^32 + 1 and 2^40 bytes in a buffer
 of 2^41, seg0, nsegs, the byte totals, and every refusal."""
 import os
@@ -21,7 +21,7 @@ def sim():
     r = subprocess.run(["make", "-C", SIMDIR, "-f", "far_plan.mk"], capture_output=True, text=True)
     assert r.returncode == 0, r.stdout + r.stderr
     mk = open(os.path.join(SIMDIR, "far_plan.mk")).read()
-    assert "-fsanitize=address,undefined" in mk and all(h in mk for h in ("nlzm_read_plan.h", "nlzm_planes_plan.h", "nlzm_container_plan.h", "nlzm_dedup_plan.h"))
+    assert "-fsanitize=address,undefined" in mk and all(h in mk for h in ("nlzm_read_plan.h", "nlzm_planes_plan.h", "nlzm_container_plan.h", "nlzm_dedup_plan.h", "nlzm_units.h"))
     return SIM
 
 
@@ -135,11 +135,16 @@ def test_refusals(sim, tmp_path):
 
 def test_library_and_harness_read_the_same_headers():
     csrc = os.path.join(os.path.dirname(HERE), "nlzm_amd", "csrc")
+    # the library's host file and the roles' harness use the shared table (nlzm_units.h, through the headers they include) and hold no copy of it
     host = open(os.path.join(csrc, "nlzm_hip_dedup.cpp")).read()
-    assert '#include "nlzm_dedup_plan.h"' in host and "dedup::prefix_of" in host and "std::vector<unsigned long long> prefix_of" not in host
-    assert "prefix_of(uint32_t n, unsigned long long unit, Len len)" in open(os.path.join(csrc, "nlzm_dedup_plan.h")).read()
+    assert '#include "nlzm_dedup_plan.h"' in host and "units::prefix(" in host and "std::vector<unsigned long long> prefix" not in host
+    roles = open(os.path.join(SIMDIR, "dedup_sim.cpp")).read()
+    assert "units::prefix(" in roles and "std::vector<unsigned long long> prefix" not in roles and "nlzm_units.h" in open(os.path.join(SIMDIR, "dedup.mk")).read()
+    assert "prefix(uint32_t n, unsigned long long unit, Len len_of)" in open(os.path.join(csrc, "nlzm_units.h")).read()
+    for name in ("nlzm_dedup.h", "nlzm_read_plan.h"):
+        assert '#include "nlzm_units.h"' in open(os.path.join(csrc, name)).read(), name
     harness = open(os.path.join(SIMDIR, "far_plan_sim.cpp")).read()
-    for name in ("crc::SegTable", "planes::Table", "planes::Layout", "planes::check_ranges(", "container::make_ranges_plan(", "dedup::prefix_of(", "dedup::check_ranges("):
+    for name in ("crc::SegTable", "planes::Table", "planes::Layout", "planes::check_ranges(", "container::make_ranges_plan(", "units::prefix(", "dedup::check_ranges("):
         assert name in harness, name
     for src, name in (("nlzm_hip_crc.cpp", "crc::SegTable"), ("nlzm_hip_planes.cpp", "planes::Table"), ("nlzm_hip_blocks.cpp", "make_ranges_plan(")):
         assert name in open(os.path.join(csrc, src)).read(), (src, name)

@@ -45,10 +45,11 @@ def test_library_and_harnesses_read_one_header():
     csrc = os.path.join(os.path.dirname(HERE), "nlzm_amd", "csrc")
     host = open(os.path.join(csrc, "nlzm_hip_planes.cpp")).read()
     assert '#include "nlzm_planes_plan.h"' in host
-    for name in ("planes::check_ranges(", "planes::check_elems(", "planes::Table", "planes::Layout", "planes::runs("):
+    for name in ("planes::check_ranges(", "planes::check_elems(", "planes::check_typed_ranges(", "planes::Table", "planes::Layout", "planes::runs("):
         assert name in host, name
+    assert "runs over" not in host                  # (the typed calls' range check is the plan's, not a copy in the host file)
     harness = open(os.path.join(SIMDIR, "planes_plan_sim.cpp")).read()
-    for name in ("planes::check_ranges(", "planes::Table", "planes::Layout", "planes::runs("):
+    for name in ("planes::check_ranges(", "planes::check_typed_ranges(", "planes::Table", "planes::Layout", "planes::runs("):
         assert name in harness, name
     plan = open(os.path.join(csrc, "nlzm_planes_plan.h")).read()
     assert "hip_runtime" not in plan and "__device__" not in plan          # (no device in it)
