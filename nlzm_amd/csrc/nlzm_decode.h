@@ -40,7 +40,7 @@ namespace NLZM_DEC_NS {
 #ifndef NLZM_DEC_RING
 #define NLZM_DEC_RING 65536
 #endif
-constexpr uint32_t kRing = NLZM_DEC_RING;           // bytes of the output ring (a test build shrinks it: tests/host_sim/decode.mk)
+constexpr uint32_t kRing = NLZM_DEC_RING;           // bytes of the output ring (a test build shrinks it: tests/host_sim/Makefile)
 constexpr uint32_t kMaxMatch = 7 + 255 + 5;         // lv <= 7 + 15 * 16 + 15, match_min <= 5
 constexpr uint32_t kFlush = kRing - 288 < 8192 ? kRing - 288 : 8192;    // unflushed bytes from which the ring is flushed after an op
 static_assert((kRing & (kRing - 1)) == 0 && kRing >= 512, "the ring is a power of two, and an op's kMaxMatch bytes + what is unflushed must fit");

@@ -1,5 +1,5 @@
 // container_plan_sim.cpp -- the plan of a container compressed in sets (nlzm_amd/csrc/nlzm_container_plan.h) on its own: no device, no library.
-// TEST HARNESS ONLY (tests/test_container_plan.py; built by container_plan.mk with -fsanitize=address,undefined).
+// TEST HARNESS ONLY (tests/test_container_plan.py; built by the Makefile with -fsanitize=address,undefined).
 //
 //   container_plan_sim sweep                                 every combination of the issue's table, checked here (see check()); one line each
 //   container_plan_sim plan <n> <nblocks> <set_blocks> <capacity>    one plan, printed: the test holds the block ranges to shard.block_range

@@ -14,16 +14,19 @@
 #define NLZM_SIM 1
 #include "../../nlzm_amd/csrc/nlzm_crc.h"
 #include "../../nlzm_amd/csrc/nlzm_read_plan.h"
+#include "sim_kit.h"
+#include "xw_sim.cpp"
 
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
-#include <sys/mman.h>
-#include <unistd.h>
 
 #include <vector>
 
 using namespace nlzm;
+using namespace simkit;
+
+const char simkit::kProgram[] = "crc_sim";
 
 namespace {
 
@@ -56,30 +59,6 @@ std::vector<uint32_t> run(const uint8_t *buf, uint64_t buf_len, const std::vecto
     std::vector<unsigned long long> small(k, sizeof(crc::CombineLds));
     xw::launch(k, threads, small.data(), entry, &P);
     return out;
-}
-
-// `bytes` usable bytes between two PROT_NONE pages
-struct Guarded {
-    uint8_t *lo = nullptr, *hi = nullptr;           // first usable byte, the guard page behind
-    void make(size_t bytes)
-    {
-        const size_t pg = (size_t)sysconf(_SC_PAGESIZE), n = (bytes + pg - 1) / pg * pg;
-        uint8_t *m = (uint8_t *)mmap(nullptr, n + 2 * pg, PROT_READ | PROT_WRITE, MAP_PRIVATE | MAP_ANONYMOUS, -1, 0);
-        if (m == MAP_FAILED || mprotect(m, pg, PROT_NONE) || mprotect(m + pg + n, pg, PROT_NONE)) { fprintf(stderr, "crc_sim: no guarded buffer\n"); exit(2); }
-        lo = m + pg; hi = m + pg + n;
-    }
-};
-
-std::vector<uint8_t> slurp(const char *path)
-{
-    std::vector<uint8_t> b;
-    FILE *f = fopen(path, "rb");
-    if (!f) { fprintf(stderr, "cannot read %s\n", path); exit(2); }
-    fseek(f, 0, SEEK_END); const long sz = ftell(f); fseek(f, 0, SEEK_SET);
-    b.resize((size_t)sz);
-    if (sz && fread(b.data(), 1, (size_t)sz, f) != (size_t)sz) { fprintf(stderr, "short read\n"); exit(2); }
-    fclose(f);
-    return b;
 }
 
 }  // namespace

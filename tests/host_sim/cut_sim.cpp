@@ -13,16 +13,19 @@
 // entry short, which must report the same number of cuts and leave the entry behind the list alone.
 #define NLZM_SIM 1
 #include "../../nlzm_amd/csrc/nlzm_cut.h"
+#include "sim_kit.h"
+#include "xw_sim.cpp"
 
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
-#include <sys/mman.h>
-#include <unistd.h>
 
 #include <vector>
 
 using namespace nlzm;
+using namespace simkit;
+
+const char simkit::kProgram[] = "cut_sim";
 
 namespace {
 
@@ -69,30 +72,6 @@ Result run(const uint8_t *src, uint64_t n, uint32_t avg_bits, uint64_t min_len, 
         for (unsigned long long i = 0; i + 1 < res[0]; i++) if (shorter[i] != list[i]) { fprintf(stderr, "cut_sim: the short list differs\n"); exit(3); }
     }
     return R;
-}
-
-// `bytes` usable bytes between two PROT_NONE pages
-struct Guarded {
-    uint8_t *lo = nullptr, *hi = nullptr;           // first usable byte, the guard page behind
-    void make(size_t bytes)
-    {
-        const size_t pg = (size_t)sysconf(_SC_PAGESIZE), n = (bytes + pg - 1) / pg * pg;
-        uint8_t *m = (uint8_t *)mmap(nullptr, n + 2 * pg, PROT_READ | PROT_WRITE, MAP_PRIVATE | MAP_ANONYMOUS, -1, 0);
-        if (m == MAP_FAILED || mprotect(m, pg, PROT_NONE) || mprotect(m + pg + n, pg, PROT_NONE)) { fprintf(stderr, "cut_sim: no guarded buffer\n"); exit(2); }
-        lo = m + pg; hi = m + pg + n;
-    }
-};
-
-std::vector<uint8_t> slurp(const char *path)
-{
-    std::vector<uint8_t> b;
-    FILE *f = fopen(path, "rb");
-    if (!f) { fprintf(stderr, "cannot read %s\n", path); exit(2); }
-    fseek(f, 0, SEEK_END); const long sz = ftell(f); fseek(f, 0, SEEK_SET);
-    b.resize((size_t)sz);
-    if (sz && fread(b.data(), 1, (size_t)sz, f) != (size_t)sz) { fprintf(stderr, "short read\n"); exit(2); }
-    fclose(f);
-    return b;
 }
 
 void print(const Result &R, const char *end)

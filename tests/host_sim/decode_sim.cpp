@@ -17,73 +17,23 @@
 #define NLZM_SIM 1
 #include "../../nlzm_amd/csrc/nlzm_decode.h"
 #include "../../nlzm_amd/csrc/nlzm_host_decode.h"
+#include "sim_kit.h"
+#include "xw_sim.cpp"
 
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
-#include <sys/mman.h>
-#include <unistd.h>
 
 #include <map>
 #include <string>
 #include <vector>
 
 using namespace nlzm;
+using namespace simkit;
+
+const char simkit::kProgram[] = "decode_sim";
 
 namespace {
-
-constexpr size_t kCanary = 4096;
-constexpr uint8_t kPoison = 0xA5;
-
-// a buffer of n bytes between two PROT_NONE pages: kMid at a chosen misalignment with canaries on both sides, kFront starting right behind
-// the page in front, kBack with its last byte flush against the page behind; whatever else the pages enclose is canary
-enum Place { kMid, kFront, kBack };
-struct Guarded {
-    uint8_t *map = nullptr, *lo = nullptr, *hi = nullptr, *q = nullptr;      // [lo, hi): readable and writable; q: the buffer
-    size_t map_len = 0, n = 0;
-    Guarded() = default;
-    Guarded(const Guarded &) = delete;
-    Guarded &operator=(const Guarded &) = delete;
-    ~Guarded() { if (map) munmap(map, map_len); }
-    void make(size_t bytes, size_t misalign, uint8_t fill, Place place = kMid)
-    {
-        if (map) { munmap(map, map_len); map = nullptr; }
-        const size_t pg = (size_t)sysconf(_SC_PAGESIZE), room = (bytes + 2 * kCanary + 64 + pg - 1) / pg * pg;
-        map_len = room + 2 * pg;
-        map = (uint8_t *)mmap(nullptr, map_len, PROT_READ | PROT_WRITE, MAP_PRIVATE | MAP_ANONYMOUS, -1, 0);
-        if (map == MAP_FAILED || mprotect(map, pg, PROT_NONE) || mprotect(map + pg + room, pg, PROT_NONE)) { fprintf(stderr, "decode_sim: no guarded buffer\n"); exit(2); }
-        lo = map + pg; hi = lo + room; n = bytes;
-        memset(lo, kPoison, room);
-        q = place == kFront ? lo : place == kBack ? hi - bytes : lo + kCanary + misalign;
-        memset(q, fill, bytes);
-    }
-    uint8_t *p() { return q; }
-    bool intact() const
-    {
-        for (const uint8_t *c = lo; c < q; c++) if (*c != kPoison) return false;
-        for (const uint8_t *c = q + n; c < hi; c++) if (*c != kPoison) return false;
-        return true;
-    }
-};
-
-std::vector<uint8_t> slurp(const char *path)
-{
-    std::vector<uint8_t> b;
-    FILE *f = fopen(path, "rb");
-    if (!f) { fprintf(stderr, "cannot read %s\n", path); exit(2); }
-    fseek(f, 0, SEEK_END); const long sz = ftell(f); fseek(f, 0, SEEK_SET);
-    b.resize((size_t)sz);
-    if (sz && fread(b.data(), 1, (size_t)sz, f) != (size_t)sz) { fprintf(stderr, "short read\n"); exit(2); }
-    fclose(f);
-    return b;
-}
-void spill(const char *path, const uint8_t *p, size_t n)
-{
-    FILE *f = fopen(path, "wb");
-    if (!f) { fprintf(stderr, "cannot write %s\n", path); exit(2); }
-    if (n) fwrite(p, 1, n, f);
-    fclose(f);
-}
 
 struct LaunchPack { std::vector<dec::StreamArgs> a; std::vector<dec::StreamResult> r; };
 void entry(void *arg)

@@ -1,5 +1,5 @@
 // decode_small_sim.cpp -- the decoder role at the ring of decode_small_kernel (nlzm_amd/csrc/nlzm_decode_small.hip: 16 KiB), run on the CPU,
-// every lane a fiber, beside the host decoder.  TEST HARNESS ONLY (tests/test_decode_small_ring_sim.py; built by decode_small.mk with
+// every lane a fiber, beside the host decoder.  TEST HARNESS ONLY (tests/test_decode_small_ring_sim.py; built by the Makefile with
 // -DNLZM_DEC_RING=16384).  The buffers, the launch and the result line are decode_sim.cpp's, which this file takes in whole (its main renamed).
 //
 //   decode_small_sim decode  <stream> <out> <misalign>      one stream, the destination `misalign` bytes off a 16-byte boundary, between

@@ -12,6 +12,7 @@
 // rep < member; an index is a member at most once a round; a representative, or a member that was found equal, never shows up again -- so every
 // element is resolved exactly once.  Afterwards: the rounds are at most the largest number of distinct contents in a group.
 #include "../../nlzm_amd/csrc/nlzm_dedup_plan.h"
+#include "sim_kit.h"
 
 #include <stdio.h>
 #include <stdlib.h>
@@ -23,6 +24,7 @@
 #include <vector>
 
 using namespace nlzm;
+using simkit::slurp;
 
 namespace {
 
@@ -144,18 +146,6 @@ int sweep()
     }
     printf("sweep: cases=%lu\n", cases);
     return 0;
-}
-
-std::vector<uint8_t> slurp(const char *path)
-{
-    std::vector<uint8_t> b;
-    FILE *f = fopen(path, "rb");
-    if (!f) { fprintf(stderr, "cannot read %s\n", path); exit(2); }
-    fseek(f, 0, SEEK_END); const long sz = ftell(f); fseek(f, 0, SEEK_SET);
-    b.resize((size_t)sz);
-    if (sz && fread(b.data(), 1, (size_t)sz, f) != (size_t)sz) { fprintf(stderr, "short read\n"); exit(2); }
-    fclose(f);
-    return b;
 }
 
 }  // namespace

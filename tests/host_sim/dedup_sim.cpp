@@ -19,16 +19,19 @@
 // is followed by a word that has to stay as it was, and every word of it has to be written.
 #define NLZM_SIM 1
 #include "../../nlzm_amd/csrc/nlzm_dedup.h"
+#include "sim_kit.h"
+#include "xw_sim.cpp"
 
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
-#include <sys/mman.h>
-#include <unistd.h>
 
 #include <vector>
 
 using namespace nlzm;
+using namespace simkit;
+
+const char simkit::kProgram[] = "dedup_sim";
 
 namespace {
 
@@ -91,31 +94,6 @@ std::vector<uint32_t> verdicts(const uint8_t *buf, const std::vector<dedup::Pair
     return eq;
 }
 
-// one mapping: a PROT_NONE page, region A, a PROT_NONE page, region B, a PROT_NONE page
-struct Guarded {
-    uint8_t *base = nullptr, *a_lo = nullptr, *a_hi = nullptr, *b_lo = nullptr, *b_hi = nullptr;
-    size_t room = 0;
-    void make(size_t bytes)
-    {
-        const size_t pg = (size_t)sysconf(_SC_PAGESIZE), n = (bytes + pg - 1) / pg * pg;
-        uint8_t *m = (uint8_t *)mmap(nullptr, 2 * n + 3 * pg, PROT_READ | PROT_WRITE, MAP_PRIVATE | MAP_ANONYMOUS, -1, 0);
-        if (m == MAP_FAILED || mprotect(m, pg, PROT_NONE) || mprotect(m + pg + n, pg, PROT_NONE) || mprotect(m + 2 * pg + 2 * n, pg, PROT_NONE)) { fprintf(stderr, "dedup_sim: no guarded buffer\n"); exit(2); }
-        base = m; a_lo = m + pg; a_hi = a_lo + n; b_lo = a_hi + pg; b_hi = b_lo + n; room = n;
-    }
-};
-
-std::vector<uint8_t> slurp(const char *path)
-{
-    std::vector<uint8_t> b;
-    FILE *f = fopen(path, "rb");
-    if (!f) { fprintf(stderr, "cannot read %s\n", path); exit(2); }
-    fseek(f, 0, SEEK_END); const long sz = ftell(f); fseek(f, 0, SEEK_SET);
-    b.resize((size_t)sz);
-    if (sz && fread(b.data(), 1, (size_t)sz, f) != (size_t)sz) { fprintf(stderr, "short read\n"); exit(2); }
-    fclose(f);
-    return b;
-}
-
 bool shape_ok(unsigned threads, unsigned blocks) { return threads && threads % 64 == 0 && threads <= 1024 && blocks; }
 
 }  // namespace
@@ -126,8 +104,9 @@ int main(int argc, char **argv)
     const std::vector<uint8_t> data = slurp(argv[1]);
     FILE *f = fopen(argv[2], "r");
     if (!f) { fprintf(stderr, "cannot read %s\n", argv[2]); return 2; }
-    Guarded g;
-    g.make(data.size() + 16);
+    Regions map;                                    // ONE mapping, region A and region B: the two strings of a pair are offsets from one base
+    map.make(2, data.size() + 16);
+    const struct { uint8_t *base, *a_lo, *a_hi, *b_lo, *b_hi; size_t room; } g{ map.base, map.lo(0), map.hi(0), map.lo(1), map.hi(1), map.room };
     char kind[8];
     while (fscanf(f, "%7s", kind) == 1) {
         unsigned threads, blocks;

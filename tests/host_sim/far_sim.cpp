@@ -22,6 +22,8 @@
 #include "../../nlzm_amd/csrc/nlzm_dedup_plan.h"
 #include "../../nlzm_amd/csrc/nlzm_planes_plan.h"
 #include "../../nlzm_amd/csrc/nlzm_read_plan.h"
+#include "sim_kit.h"
+#include "xw_sim.cpp"
 
 #include <stdio.h>
 #include <stdlib.h>
@@ -32,6 +34,7 @@
 #include <vector>
 
 using namespace nlzm;
+using simkit::slurp;
 
 namespace {
 
@@ -71,18 +74,6 @@ uint32_t crc32_of(const uint8_t *p, size_t n)
     uint32_t c = 0xFFFFFFFFu;
     for (size_t i = 0; i < n; i++) c = table[(c ^ p[i]) & 0xFFu] ^ (c >> 8);
     return c ^ 0xFFFFFFFFu;
-}
-
-std::vector<uint8_t> slurp(const char *path)
-{
-    std::vector<uint8_t> b;
-    FILE *f = fopen(path, "rb");
-    if (!f) { fprintf(stderr, "cannot read %s\n", path); exit(2); }
-    fseek(f, 0, SEEK_END); const long sz = ftell(f); fseek(f, 0, SEEK_SET);
-    b.resize((size_t)sz);
-    if (sz && fread(b.data(), 1, (size_t)sz, f) != (size_t)sz) { fprintf(stderr, "short read\n"); exit(2); }
-    fclose(f);
-    return b;
 }
 
 uint8_t *far_map(unsigned long long n)

@@ -1,5 +1,5 @@
 // index_sim.cpp -- the sidecar index's parser, validators and writer (nlzm_amd/csrc/nlzm_index.h) on their own: no device, no library.
-// TEST HARNESS ONLY (tests/test_index_sim.py; built by index.mk with -fsanitize=address,undefined).
+// TEST HARNESS ONLY (tests/test_index_sim.py; built by the Makefile with -fsanitize=address,undefined).
 //
 //   index_sim roundtrip             the writer's text for every version word for word, and writer -> parser -> the same index, for 1, 5 and 300 blocks
 //   index_sim judge <idx> <size>    the index text in <idx> through the parser, then through BOTH validators, each with what x takes of an index and

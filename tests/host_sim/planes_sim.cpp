@@ -16,16 +16,18 @@
 #define NLZM_SIM 1
 #include "../../nlzm_amd/csrc/nlzm_planes.h"
 #include "../../nlzm_amd/csrc/nlzm_planes_plan.h"
+#include "sim_kit.h"
+#include "xw_sim.cpp"
 
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
-#include <sys/mman.h>
-#include <unistd.h>
 
 #include <vector>
 
 using namespace nlzm;
+
+const char simkit::kProgram[] = "planes_sim";
 
 namespace {
 
@@ -48,31 +50,19 @@ uint32_t crc32_of(const uint8_t *p, size_t n)
     return c ^ 0xFFFFFFFFu;
 }
 
-std::vector<uint8_t> slurp(const char *path)
-{
-    std::vector<uint8_t> b;
-    FILE *f = fopen(path, "rb");
-    if (!f) { fprintf(stderr, "cannot read %s\n", path); exit(2); }
-    fseek(f, 0, SEEK_END); const long sz = ftell(f); fseek(f, 0, SEEK_SET);
-    b.resize((size_t)sz);
-    if (sz && fread(b.data(), 1, (size_t)sz, f) != (size_t)sz) { fprintf(stderr, "short read\n"); exit(2); }
-    fclose(f);
-    return b;
-}
-
 }  // namespace
 
 int main(int argc, char **argv)
 {
     if (argc != 3) { fprintf(stderr, "usage: see the head of planes_sim.cpp\n"); return 2; }
-    const std::vector<uint8_t> data = slurp(argv[1]);
+    const std::vector<uint8_t> data = simkit::slurp(argv[1]);
     FILE *f = fopen(argv[2], "r");
     if (!f) { fprintf(stderr, "cannot read %s\n", argv[2]); return 2; }
     // the slots: ONE mapping, [PROT_NONE page][room][PROT_NONE page][room] ... [PROT_NONE page], so that every source is an offset from its first byte
-    const size_t pg = (size_t)sysconf(_SC_PAGESIZE), room = (3 * (size_t)planes::kSegment + 64 + pg - 1) / pg * pg, stride = room + pg;
-    uint8_t *map = (uint8_t *)mmap(nullptr, kSlots * stride + pg, PROT_READ | PROT_WRITE, MAP_PRIVATE | MAP_ANONYMOUS, -1, 0);
-    if (map == MAP_FAILED) { fprintf(stderr, "planes_sim: no mapping\n"); return 2; }
-    for (uint32_t s = 0; s <= kSlots; s++) if (mprotect(map + s * stride, pg, PROT_NONE)) { fprintf(stderr, "planes_sim: no guard page\n"); return 2; }
+    simkit::Regions slots;
+    slots.make(kSlots, 3 * (size_t)planes::kSegment + 64);
+    uint8_t *const map = slots.base;
+    const size_t pg = simkit::page(), room = slots.room, stride = slots.stride;
     const size_t dstride = room + 256;
     uint8_t *dst = nullptr;
     if (posix_memalign((void **)&dst, 64, kSlots * dstride)) return 2;

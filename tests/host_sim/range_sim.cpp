@@ -28,66 +28,22 @@
 #include "../../nlzm_amd/csrc/nlzm_host_decode.h"
 #include "../../nlzm_amd/csrc/nlzm_range.h"
 #include "../../nlzm_amd/csrc/nlzm_read_plan.h"
+#include "sim_kit.h"
+#include "xw_sim.cpp"
 
 #include <malloc.h>
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
-#include <sys/mman.h>
-#include <unistd.h>
 
 #include <vector>
 
 using namespace nlzm;
+using namespace simkit;
+
+const char simkit::kProgram[] = "range_sim";
 
 namespace {
-
-constexpr size_t kCanary = 4096;
-constexpr uint8_t kPoison = 0xA5;
-
-// a buffer of n bytes at a chosen misalignment between two canaries (as decode_sim.cpp's)
-struct Canaried {
-    std::vector<uint8_t> mem;
-    size_t off = 0, n = 0;
-    void make(size_t bytes, size_t misalign, uint8_t fill)
-    {
-        n = bytes;
-        mem.assign(2 * kCanary + bytes + 64, kPoison);
-        off = kCanary + ((64 - ((uintptr_t)mem.data() + kCanary) % 64) % 64) + misalign;
-        memset(mem.data() + off, fill, bytes);
-    }
-    uint8_t *p() { return mem.data() + off; }
-    bool intact() const
-    {
-        for (size_t i = 0; i < off; i++) if (mem[i] != kPoison) return false;
-        for (size_t i = off + n; i < mem.size(); i++) if (mem[i] != kPoison) return false;
-        return true;
-    }
-};
-
-// `bytes` usable bytes (rounded up to pages) between two PROT_NONE pages (as crc_sim.cpp's)
-struct Guarded {
-    uint8_t *lo = nullptr, *hi = nullptr;
-    void make(size_t bytes)
-    {
-        const size_t pg = (size_t)sysconf(_SC_PAGESIZE), n = (bytes + pg - 1) / pg * pg;
-        uint8_t *m = (uint8_t *)mmap(nullptr, n + 2 * pg, PROT_READ | PROT_WRITE, MAP_PRIVATE | MAP_ANONYMOUS, -1, 0);
-        if (m == MAP_FAILED || mprotect(m, pg, PROT_NONE) || mprotect(m + pg + n, pg, PROT_NONE)) { fprintf(stderr, "range_sim: no guarded buffer\n"); exit(2); }
-        lo = m + pg; hi = m + pg + n;
-    }
-};
-
-std::vector<uint8_t> slurp(const char *path)
-{
-    std::vector<uint8_t> b;
-    FILE *f = fopen(path, "rb");
-    if (!f) { fprintf(stderr, "cannot read %s\n", path); exit(2); }
-    fseek(f, 0, SEEK_END); const long sz = ftell(f); fseek(f, 0, SEEK_SET);
-    b.resize((size_t)sz);
-    if (sz && fread(b.data(), 1, (size_t)sz, f) != (size_t)sz) { fprintf(stderr, "short read\n"); exit(2); }
-    fclose(f);
-    return b;
-}
 
 uint32_t rng_state = 1;
 uint32_t rnd() { rng_state = rng_state * 1664525u + 1013904223u; return rng_state >> 8; }

@@ -1,5 +1,5 @@
 // ranges_plan_sim.cpp -- the plan of a call on ranges of the caller's choosing (nlzm_amd/csrc/nlzm_container_plan.h, make_ranges_plan) on its own: no
-// device, no library.  TEST HARNESS ONLY (tests/test_ranges_plan.py; built by ranges_plan.mk with -fsanitize=address,undefined).
+// device, no library.  TEST HARNESS ONLY (tests/test_ranges_plan.py; built by the Makefile with -fsanitize=address,undefined).
 //
 //   ranges_plan_sim sweep                                    the fixed cases, checked here; one summary line
 //   ranges_plan_sim plan <n> <set_blocks> <capacity> <file>  one plan from the "off len" lines of <file>, printed:

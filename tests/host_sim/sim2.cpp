@@ -18,6 +18,7 @@
 #define NLZM_HDN
 #include "../../nlzm_amd/csrc/nlzm_v2.h"
 #include "../../oracle/nlzm_oracle.h"
+#include "xw_sim.cpp"
 
 using namespace nlzm;
 

@@ -1,5 +1,5 @@
 // stream_plan_sim.cpp -- the single stream's launch plan (nlzm_amd/csrc/nlzm_stream_plan.h) on its own: no device, no library.
-// TEST HARNESS ONLY (tests/test_stream_plan.py; built by stream_plan.mk with -fsanitize=address,undefined).
+// TEST HARNESS ONLY (tests/test_stream_plan.py; built by the Makefile with -fsanitize=address,undefined).
 //
 //   stream_plan_sim plan <free_bytes> <table_bytes> <per_chunk> <batch> <nchunks>     one plan, printed: "plan <batch> <depth>"
 #include "../../nlzm_amd/csrc/nlzm_stream_plan.h"

@@ -6,6 +6,9 @@
 // GPU, including divergence, and a cross-lane operation reached by only part of a wave is reported as an error.  So is a readlane,
 // shuffle or scan in which a live lane's source is a lane that has left the role: xw.h leaves that value undefined in both builds, and
 // the simulator does not hand out the exited fiber's last argument in its place.
+//
+// Not compiled on its own: every program that runs roles takes this file in with #include, behind its product headers, so that a program
+// is one translation unit and its dependency file names everything it was compiled from (Makefile).
 #define NLZM_SIM 1
 #include "../../nlzm_amd/csrc/xw.h"
 

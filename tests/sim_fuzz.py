@@ -12,7 +12,7 @@ first, count = int(sys.argv[1]), int(sys.argv[2])
 jobs = int(sys.argv[3]) if len(sys.argv) > 3 else 6
 kind = sys.argv[4] if len(sys.argv) > 4 else "splice"
 REAL = corpus.make("real_text", 120_000_000) if kind == "real_text" else None
-subprocess.run(["make", "-C", os.path.join("tests", "host_sim")], check=True, capture_output=True)
+subprocess.run(["make", "-C", os.path.join("tests", "host_sim"), "sim2"], check=True, capture_output=True)
 
 def one(seed):
     rng = np.random.default_rng(seed)

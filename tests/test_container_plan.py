@@ -8,15 +8,12 @@ of each other; nblocks <= capacity gives one set; the sets' byte ranges tile [0,
 prints are shard.block_range's."""
 import os
 import re
-import subprocess
 
 import pytest
 
 from nlzm_amd import shard
+from tests import simkit
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-SIMDIR = os.path.join(HERE, "host_sim")
-SIM = os.path.join(SIMDIR, "container_plan_sim_san")
 NBLOCKS = [1, 32, 64, 65, 66, 127, 128, 129, 1000, 65536]
 SET_BLOCKS = [1, 7, 32, 64]
 CAPACITY = [16, 64]
@@ -24,15 +21,14 @@ CAPACITY = [16, 64]
 
 @pytest.fixture(scope="module")
 def sim():
-    r = subprocess.run(["make", "-C", SIMDIR, "-f", "container_plan.mk"], capture_output=True, text=True)
-    assert r.returncode == 0, r.stdout + r.stderr
-    mk = open(os.path.join(SIMDIR, "container_plan.mk")).read()
-    assert "-fsanitize=address,undefined" in mk and "nlzm_container_plan.h" in mk
-    return SIM
+    sim, = simkit.build("container_plan_sim_san")
+    assert "-fsanitize=address,undefined" in simkit.compiled_with("container_plan_sim_san")
+    assert "nlzm_amd/csrc/nlzm_container_plan.h" in simkit.compiled_from("container_plan_sim_san")
+    return sim
 
 
 def run(sim, *args):
-    r = subprocess.run([sim] + [str(a) for a in args], capture_output=True, text=True, timeout=600)
+    r = simkit.sh([sim, *args], 600)
     assert r.returncode == 0 and "container_plan_sim: OK" in r.stdout, r.stdout[-2000:] + r.stderr[-2000:]
     return r.stdout
 
@@ -45,9 +41,9 @@ def test_sweep(sim):
 
 
 def test_library_and_harness_read_one_header():
-    csrc = os.path.join(os.path.dirname(HERE), "nlzm_amd", "csrc")
+    csrc = os.path.join(simkit.ROOT, "nlzm_amd", "csrc")
     assert '#include "nlzm_container_plan.h"' in open(os.path.join(csrc, "nlzm_hip_blocks.cpp")).read()
-    assert "nlzm_container_plan.h" in open(os.path.join(SIMDIR, "container_plan_sim.cpp")).read()
+    assert "nlzm_container_plan.h" in open(os.path.join(simkit.SIMDIR, "container_plan_sim.cpp")).read()
     text = open(os.path.join(csrc, "nlzm_container_plan.h")).read()
     assert "hip" not in text.lower().replace("nlzm_hip", "")          # no device in it
 

@@ -6,7 +6,6 @@ byte flush against the PROT_NONE page behind the buffer, so a read outside the r
 list is dealt to eight harness processes, each of which runs its share in one go and prints one line per case: 8 s on eight cores
 from a clean tree (4 s of it the build), 30 s of CPU time in all."""
 import os
-import subprocess
 import zlib
 from concurrent.futures import ThreadPoolExecutor
 
@@ -14,22 +13,17 @@ import numpy as np
 import pytest
 
 from nlzm_amd import corpus
+from tests import simkit
+from tests.simkit import sh
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-SIMDIR = os.path.join(HERE, "host_sim")
-SIM = os.path.join(SIMDIR, "crc_sim_san")
+SIM = os.path.join(simkit.SIMDIR, "crc_sim_san")
 SHARDS = 8
 SEEDS = [0, 0x9E3779B9]
 
 
-def sh(cmd, timeout=600):
-    return subprocess.run([str(c) for c in cmd], capture_output=True, text=True, timeout=timeout)
-
-
 @pytest.fixture(scope="module")
 def sim(tmp_path_factory):
-    r = subprocess.run(["make", "-C", SIMDIR, "-f", "crc.mk"], capture_output=True, text=True)
-    assert r.returncode == 0, r.stdout + r.stderr
+    simkit.build("crc_sim_san")
     d = tmp_path_factory.mktemp("crc_sim")
     (d / "g.txt").write_text("G\n")
     (d / "none.bin").write_bytes(b"")

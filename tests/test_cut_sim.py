@@ -6,34 +6,27 @@ flush against the PROT_NONE page behind the buffer, so a read outside the input 
 buffer is followed by a guard word, and the selection runs again with a list one entry short.  The case list is dealt to eight harness
 processes."""
 import os
-import subprocess
 from concurrent.futures import ThreadPoolExecutor
 
 import numpy as np
 import pytest
 
 from nlzm_amd import corpus
-from tests import cut_model
+from tests import cut_model, simkit
+from tests.simkit import sh
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-SIMDIR = os.path.join(HERE, "host_sim")
-SIM = os.path.join(SIMDIR, "cut_sim_san")
+SIM = os.path.join(simkit.SIMDIR, "cut_sim_san")
 SHARDS = 8
 AVG_BITS = [1, 4, 12]
 MAX_LENS = [32, 48, 100, 1000]
 KINDS = ["random", "text", "zeros", "ones"]
 
 
-def sh(cmd, timeout=600):
-    return subprocess.run([str(c) for c in cmd], capture_output=True, text=True, timeout=timeout)
-
-
 @pytest.fixture(scope="module")
 def sim(tmp_path_factory):
-    r = subprocess.run(["make", "-C", SIMDIR, "-f", "cut.mk"], capture_output=True, text=True)
-    assert r.returncode == 0, r.stdout + r.stderr
-    mk = open(os.path.join(SIMDIR, "cut.mk")).read()
-    assert "-fsanitize=undefined" in mk and "nlzm_cut.h" in mk
+    simkit.build("cut_sim_san")
+    assert "-fsanitize=undefined" in simkit.compiled_with("cut_sim_san")
+    assert "nlzm_amd/csrc/nlzm_cut.h" in simkit.compiled_from("cut_sim_san")
     d = tmp_path_factory.mktemp("cut_sim")
     (d / "g.txt").write_text("G\n")
     (d / "none.bin").write_bytes(b"")

@@ -19,18 +19,15 @@ import hashlib
 import json
 import os
 import re
-import subprocess
-from concurrent.futures import ThreadPoolExecutor
 
 import numpy as np
 import pytest
 
 from nlzm_amd import corpus, shard
-from tests import cases, oracle_py
+from tests import cases, oracle_py, simkit
+from tests.simkit import sh
 
 HERE = os.path.dirname(os.path.abspath(__file__))
-SIMDIR = os.path.join(HERE, "host_sim")
-SIM, SIM_TINY, SIM_SAN = (os.path.join(SIMDIR, n) for n in ("decode_sim", "decode_sim_tiny", "decode_sim_san"))
 WORKERS = max(1, min(8, os.cpu_count() or 2))
 
 NAMES = ["empty", "one_byte", "tiny_1000", "under_2k", "chunk_plus1", "overlap_265", "text_200k_w15", "runs_300k_w18", "random_100k_w15",
@@ -53,10 +50,6 @@ def case_of(name):
     return next(c for c in cases.CASES if c[0] == name)
 
 
-def sh(cmd, timeout=600):
-    return subprocess.run([str(c) for c in cmd], capture_output=True, text=True, timeout=timeout)
-
-
 def edge_input(ring, d_off, prefix):
     """prefix + a random block B of 300 bytes + D - 300 random bytes + B again: the second B is a match at distance exactly D"""
     npre = {"0": 0, "37": 37, "1000": 1000, "half": ring // 2, "minus150": ring - 150}[prefix]
@@ -73,8 +66,7 @@ def blocks_input():
 
 @pytest.fixture(scope="module")
 def runs(tmp_path_factory):
-    r = subprocess.run(["make", "-j3", "-C", SIMDIR, "-f", "decode.mk"], capture_output=True, text=True)     # (three builds of the harness, beside each other)
-    assert r.returncode == 0, r.stdout + r.stderr
+    SIM, SIM_TINY, SIM_SAN = simkit.build("decode_sim", "decode_sim_tiny", "decode_sim_san", jobs=3)     # (three builds of the harness, beside each other)
     d = tmp_path_factory.mktemp("decode_sim")
     streams, inputs = {}, {}
     for n in NAMES:
@@ -113,16 +105,15 @@ def runs(tmp_path_factory):
     for n in HEX:
         jobs.append((("hex", n), [SIM, "decode", d / f"{n}.hex.nlzm", d / f"{n}.hex.out"]))
     jobs.append((("split",), [SIM_SAN, "split", d / "split.nlzm"]))
-    ex = ThreadPoolExecutor(WORKERS)
-    futs = {key: ex.submit(sh, cmd) for key, cmd in jobs}
-    yield {"futs": futs, "dir": d, "streams": streams, "inputs": inputs, "ring": ring, "edge": edge, "blocks": (bdata.tobytes(), branges)}
-    ex.shutdown(wait=False, cancel_futures=True)
+    started = simkit.Runs(WORKERS)
+    for key, cmd in jobs:
+        started.submit(key, cmd)
+    yield {"runs": started, "dir": d, "streams": streams, "inputs": inputs, "ring": ring, "edge": edge, "blocks": (bdata.tobytes(), branges)}
+    started.close()
 
 
 def ok(runs, key):
-    r = runs["futs"][key].result()
-    assert r.returncode == 0 and "decode_sim: OK" in r.stdout, r.stdout[-1500:] + r.stderr[-1500:]      # (3 / 4: the simulator's own checks and its watchdog)
-    return r.stdout
+    return runs["runs"].ok(key, "decode_sim: OK").stdout
 
 
 def field(out, name):

@@ -1,6 +1,6 @@
 """CPU suite: the decoder role at the ring of decode_small_kernel (nlzm_amd/csrc/nlzm_decode_small.hip, 16 KiB), compiled for the host with
-every GPU lane a fiber (tests/host_sim/decode_small_sim.cpp, decode_small.mk), against the host decoder and against the 64 KiB build of
-tests/host_sim/decode.mk.
+every GPU lane a fiber (tests/host_sim/decode_small_sim.cpp; decode_small_sim in tests/host_sim/Makefile), against the host decoder and
+against the 64 KiB build beside it there (decode_sim).
 
 What a smaller ring changes is where a match's bytes come from: distances up to the ring are served from LDS, farther ones from memory, and
 the unflushed part of the ring is a larger share of it.  So: streams whose matches reach 16 KiB + 1 .. 64 KiB back (the big ring's side there, the
@@ -12,18 +12,14 @@ All runs (one process each) start together when the first test asks for one; eve
 import json
 import os
 import re
-import subprocess
-from concurrent.futures import ThreadPoolExecutor
 
 import numpy as np
 import pytest
 
 from nlzm_amd import corpus
-from tests import cases, oracle_py
+from tests import cases, oracle_py, simkit
 
 HERE = os.path.dirname(os.path.abspath(__file__))
-SIMDIR = os.path.join(HERE, "host_sim")
-SMALL, BIG = os.path.join(SIMDIR, "decode_small_sim"), os.path.join(SIMDIR, "decode_sim")
 GOLDEN = os.path.join(HERE, "golden", "decode_small_ring.json")
 WORKERS = max(1, min(8, os.cpu_count() or 2))
 RING = 16384
@@ -45,15 +41,9 @@ def stream_input(name):
     return cases.make_case(c), c[4]
 
 
-def sh(cmd, timeout=900):
-    return subprocess.run([str(c) for c in cmd], capture_output=True, text=True, timeout=timeout)
-
-
 @pytest.fixture(scope="module")
 def runs(tmp_path_factory):
-    for mk in ("decode_small.mk", "decode.mk"):
-        r = subprocess.run(["make", "-j3", "-C", SIMDIR, "-f", mk], capture_output=True, text=True)
-        assert r.returncode == 0, r.stdout + r.stderr
+    SMALL, BIG = simkit.build("decode_small_sim", "decode_sim", jobs=3)
     d = tmp_path_factory.mktemp("decode_small_sim")
     inputs, streams = {}, {}
     for n in STREAMS + [MUTANT_OF]:       # (WRAP_OF is one of STREAMS)
@@ -71,16 +61,15 @@ def runs(tmp_path_factory):
     jobs.append((("mutants",), [SMALL, "mutants", d / f"{MUTANT_OF}.nlzm", MUTANT_SEED, MUTANT_FLIPS, MUTANT_COUNT]))
     for s in range(WRAP_SHARDS):       # (another seed per process: four different lists of six)
         jobs.append((("wrap", s), [SMALL, "mutants", d / f"{WRAP_OF}.nlzm", MUTANT_SEED + 1 + s, WRAP_FLIPS, WRAP_COUNT // WRAP_SHARDS]))
-    ex = ThreadPoolExecutor(WORKERS)
-    futs = {key: ex.submit(sh, cmd) for key, cmd in jobs}
-    yield {"futs": futs, "dir": d, "inputs": inputs, "streams": streams}
-    ex.shutdown(wait=False, cancel_futures=True)
+    started = simkit.Runs(WORKERS)
+    for key, cmd in jobs:
+        started.submit(key, cmd, timeout=900)
+    yield {"runs": started, "dir": d, "inputs": inputs, "streams": streams}
+    started.close()
 
 
 def ok(runs, key):
-    r = runs["futs"][key].result()
-    assert r.returncode == 0 and "decode_sim: OK" in r.stdout, r.stdout[-1500:] + r.stderr[-1500:]
-    return r.stdout
+    return runs["runs"].ok(key, "decode_sim: OK").stdout
 
 
 def field(out, name):

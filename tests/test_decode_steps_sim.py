@@ -16,19 +16,15 @@ import hashlib
 import json
 import os
 import re
-import subprocess
-from concurrent.futures import ThreadPoolExecutor
 
 import numpy as np
 import pytest
 
 import nlzm_amd
 from nlzm_amd import corpus, shard
-from tests import cases, oracle_py
+from tests import cases, oracle_py, simkit
 
 HERE = os.path.dirname(os.path.abspath(__file__))
-SIMDIR = os.path.join(HERE, "host_sim")
-SIM, SIM_TINY, SIM_SAN = (os.path.join(SIMDIR, n) for n in ("decode_steps_sim", "decode_steps_sim_tiny", "decode_steps_sim_san"))
 WORKERS = max(1, min(8, os.cpu_count() or 2))
 GOLD = {c["name"]: c for c in json.load(open(os.path.join(HERE, "golden", "streams.json")))["cases"]}
 
@@ -52,10 +48,6 @@ def case_of(name):
     return next(c for c in cases.CASES if c[0] == name)
 
 
-def sh(cmd, timeout=600):
-    return subprocess.run([str(c) for c in cmd], capture_output=True, text=True, timeout=timeout)
-
-
 def heads_of(stream):
     """the stream offsets of the frame headers, the terminator's last"""
     h, pos = [], 4
@@ -76,8 +68,7 @@ def cuts_of(stream):
 
 @pytest.fixture(scope="module")
 def runs(tmp_path_factory):
-    r = subprocess.run(["make", "-j3", "-C", SIMDIR, "-f", "decode_steps.mk"], capture_output=True, text=True)
-    assert r.returncode == 0, r.stdout + r.stderr
+    SIM, SIM_TINY, SIM_SAN = simkit.build("decode_steps_sim", "decode_steps_sim_tiny", "decode_steps_sim_san", jobs=3)
     d = tmp_path_factory.mktemp("decode_steps_sim")
     streams, inputs = {}, {}
     for n in FRAMES:
@@ -99,16 +90,15 @@ def runs(tmp_path_factory):
     jobs.append((("blocks",), [SIM, "blocks", d / "blocks.nlzm", d / "blocks.out"]))
     for n in SIZE_ONLY:
         jobs.append((("size", n), [SIM, "steps", d / f"{n}.nlzm", d / f"{n}.none", 1, 3, "size"]))
-    ex = ThreadPoolExecutor(WORKERS)
-    futs = {key: ex.submit(sh, cmd) for key, cmd in jobs}
-    yield {"futs": futs, "dir": d, "streams": streams, "inputs": inputs, "blocks": (bdata.tobytes(), branges)}
-    ex.shutdown(wait=False, cancel_futures=True)
+    started = simkit.Runs(WORKERS)
+    for key, cmd in jobs:
+        started.submit(key, cmd)
+    yield {"runs": started, "dir": d, "streams": streams, "inputs": inputs, "blocks": (bdata.tobytes(), branges)}
+    started.close()
 
 
 def ok(runs, key):
-    r = runs["futs"][key].result()
-    assert r.returncode == 0 and "decode_steps_sim: OK" in r.stdout, r.stdout[-1500:] + r.stderr[-1500:]
-    return r.stdout
+    return runs["runs"].ok(key, "decode_steps_sim: OK").stdout
 
 
 @pytest.mark.parametrize("name", list(FRAMES))

@@ -8,30 +8,25 @@ sound fingerprints; the identical-(off, len) and the empty shortcut; k = 1 and k
 of range lists written by this file against tests/dedup_model.py."""
 import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
 
 from nlzm_amd import corpus
-from tests import dedup_model
+from tests import dedup_model, simkit
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-SIMDIR = os.path.join(HERE, "host_sim")
-SIM = os.path.join(SIMDIR, "dedup_plan_sim_san")
 
 
 @pytest.fixture(scope="module")
 def sim():
-    r = subprocess.run(["make", "-C", SIMDIR, "-f", "dedup_plan.mk"], capture_output=True, text=True)
-    assert r.returncode == 0, r.stdout + r.stderr
-    mk = open(os.path.join(SIMDIR, "dedup_plan.mk")).read()
-    assert "-fsanitize=address,undefined" in mk and "nlzm_dedup_plan.h" in mk
-    return SIM
+    sim, = simkit.build("dedup_plan_sim_san")
+    assert "-fsanitize=address,undefined" in simkit.compiled_with("dedup_plan_sim_san")
+    assert "nlzm_amd/csrc/nlzm_dedup_plan.h" in simkit.compiled_from("dedup_plan_sim_san")
+    return sim
 
 
 def run(sim, *args):
-    r = subprocess.run([sim] + [str(a) for a in args], capture_output=True, text=True, timeout=600)
+    r = simkit.sh([sim, *args], 600)
     assert r.returncode == 0 and "dedup_plan_sim: OK" in r.stdout, r.stdout[-2000:] + r.stderr[-2000:]
     return r.stdout
 
@@ -51,10 +46,10 @@ def test_sweep(sim):
 
 
 def test_library_and_harness_read_one_header():
-    csrc = os.path.join(os.path.dirname(HERE), "nlzm_amd", "csrc")
+    csrc = os.path.join(simkit.ROOT, "nlzm_amd", "csrc")
     host = open(os.path.join(csrc, "nlzm_hip_dedup.cpp")).read()
     assert '#include "nlzm_dedup_plan.h"' in host and "dedup::class_plan(" in host and "dedup::check_ranges(" in host
-    harness = open(os.path.join(SIMDIR, "dedup_plan_sim.cpp")).read()
+    harness = open(os.path.join(simkit.SIMDIR, "dedup_plan_sim.cpp")).read()
     assert "dedup::class_plan(" in harness and "dedup::check_ranges(" in harness
 
 

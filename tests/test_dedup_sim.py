@@ -7,32 +7,26 @@ three times, each side in a region of its own between PROT_NONE pages: both at t
 flush against the page behind it.  Every output array is followed by a guard word, and the launch's shape moves from case to case.  The case
 list is dealt to eight harness processes."""
 import os
-import subprocess
 from concurrent.futures import ThreadPoolExecutor
+from functools import partial
 
 import numpy as np
 import pytest
 
 from nlzm_amd import corpus
-from tests import dedup_model
+from tests import dedup_model, simkit
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-SIMDIR = os.path.join(HERE, "host_sim")
-SIM = os.path.join(SIMDIR, "dedup_sim_san")
+SIM = os.path.join(simkit.SIMDIR, "dedup_sim_san")
 SHARDS = 8
 KINDS = ["random", "text", "zeros", "ones"]
-
-
-def sh(cmd, timeout=900):
-    return subprocess.run([str(c) for c in cmd], capture_output=True, text=True, timeout=timeout)
+sh = partial(simkit.sh, timeout=900)
 
 
 @pytest.fixture(scope="module")
 def sim(tmp_path_factory):
-    r = subprocess.run(["make", "-C", SIMDIR, "-f", "dedup.mk"], capture_output=True, text=True)
-    assert r.returncode == 0, r.stdout + r.stderr
-    mk = open(os.path.join(SIMDIR, "dedup.mk")).read()
-    assert "-fsanitize=undefined" in mk and "nlzm_dedup.h" in mk
+    simkit.build("dedup_sim_san")
+    assert "-fsanitize=undefined" in simkit.compiled_with("dedup_sim_san")
+    assert "nlzm_amd/csrc/nlzm_dedup.h" in simkit.compiled_from("dedup_sim_san")
     d = tmp_path_factory.mktemp("dedup_sim")
     (d / "g.txt").write_text("G\n")
     (d / "none.bin").write_bytes(b"")

@@ -4,13 +4,12 @@ and units::prefix (nlzm_units.h).  The harness (tests/host_sim/far_plan_sim.cpp)
 headers the library includes; every number it prints is held to Python's integers: ranges of 2^32 - 1, 2^32, 2^32 + 1 and 2^40 bytes in a buffer
 of 2^41, seg0, nsegs, the byte totals, and every refusal."""
 import os
-import subprocess
 
 import pytest
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-SIMDIR = os.path.join(HERE, "host_sim")
-SIM = os.path.join(SIMDIR, "far_plan_sim_san")
+from tests import simkit
+from tests.simkit import SIMDIR
+
 CRC_SEG, PLANES_SEG, DEDUP_SEG = 32768, 8192, 32768
 BUF = 1 << 41
 G4 = 1 << 32
@@ -18,18 +17,17 @@ G4 = 1 << 32
 
 @pytest.fixture(scope="module")
 def sim():
-    r = subprocess.run(["make", "-C", SIMDIR, "-f", "far_plan.mk"], capture_output=True, text=True)
-    assert r.returncode == 0, r.stdout + r.stderr
-    mk = open(os.path.join(SIMDIR, "far_plan.mk")).read()
-    assert "-fsanitize=address,undefined" in mk and all(h in mk for h in ("nlzm_read_plan.h", "nlzm_planes_plan.h", "nlzm_container_plan.h", "nlzm_dedup_plan.h", "nlzm_units.h"))
-    return SIM
+    sim, = simkit.build("far_plan_sim_san")
+    assert "-fsanitize=address,undefined" in simkit.compiled_with("far_plan_sim_san")
+    assert {"nlzm_amd/csrc/" + h for h in ("nlzm_read_plan.h", "nlzm_planes_plan.h", "nlzm_container_plan.h", "nlzm_dedup_plan.h", "nlzm_units.h")} <= simkit.compiled_from("far_plan_sim_san")
+    return sim
 
 
 def tables(sim, tmp_path, cases):
     """cases: (buf_len, [(off, len)]); returns per case {"crc": [...], "planes": [...], "ranges": [...], "dedup": [...]}: integers, or ("error", code, text)"""
     path = tmp_path / "cases.txt"
     path.write_text("".join(f"T {n} {CRC_SEG} {PLANES_SEG} {DEDUP_SEG} {len(r)} " + " ".join(f"{o} {l}" for o, l in r) + "\n" for n, r in cases))
-    r = subprocess.run([sim, str(path)], capture_output=True, text=True, timeout=120)
+    r = simkit.sh([sim, path], 120)
     assert r.returncode == 0 and r.stdout.endswith("far_plan_sim: OK\n"), r.stdout[-2000:] + r.stderr[-2000:]
     lines = r.stdout.splitlines()[:-1]
     assert len(lines) == 4 * len(cases)
@@ -134,12 +132,13 @@ def test_refusals(sim, tmp_path):
 
 
 def test_library_and_harness_read_the_same_headers():
-    csrc = os.path.join(os.path.dirname(HERE), "nlzm_amd", "csrc")
+    csrc = os.path.join(simkit.ROOT, "nlzm_amd", "csrc")
     # the library's host file and the roles' harness use the shared table (nlzm_units.h, through the headers they include) and hold no copy of it
     host = open(os.path.join(csrc, "nlzm_hip_dedup.cpp")).read()
     assert '#include "nlzm_dedup_plan.h"' in host and "units::prefix(" in host and "std::vector<unsigned long long> prefix" not in host
     roles = open(os.path.join(SIMDIR, "dedup_sim.cpp")).read()
-    assert "units::prefix(" in roles and "std::vector<unsigned long long> prefix" not in roles and "nlzm_units.h" in open(os.path.join(SIMDIR, "dedup.mk")).read()
+    assert "units::prefix(" in roles and "std::vector<unsigned long long> prefix" not in roles
+    assert "nlzm_amd/csrc/nlzm_units.h" in simkit.compiled_from("dedup_sim_san")
     assert "prefix(uint32_t n, unsigned long long unit, Len len_of)" in open(os.path.join(csrc, "nlzm_units.h")).read()
     for name in ("nlzm_dedup.h", "nlzm_read_plan.h"):
         assert '#include "nlzm_units.h"' in open(os.path.join(csrc, name)).read(), name

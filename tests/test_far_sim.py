@@ -4,17 +4,14 @@ GPU.  The buffer is a mapping of 2^32 + 2^22 bytes made with MAP_NORESERVE; only
 256 KiB to either side of every island, and every case stays inside those stretches).  Where the kernel refuses the mapping the harness leaves
 with status 4 and these tests skip, saying so.  The ranges longer than 2^32 are the device's: the simulator would take hours."""
 import os
-import subprocess
 import zlib
 
 import numpy as np
 import pytest
 
-from tests import far_model, planes_model
+from tests import far_model, planes_model, simkit
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-SIMDIR = os.path.join(HERE, "host_sim")
-SIM = os.path.join(SIMDIR, "far_sim_san")
+SIM = os.path.join(simkit.SIMDIR, "far_sim_san")
 SEED = 20261
 LINE, N, S = far_model.LINE, far_model.N, far_model.S
 MARGIN = 1 << 18
@@ -23,8 +20,7 @@ CRC_SEG, PLANES_SEG = 32768, 8192
 
 @pytest.fixture(scope="module")
 def far(tmp_path_factory):
-    r = subprocess.run(["make", "-C", SIMDIR, "-f", "far.mk"], capture_output=True, text=True)
-    assert r.returncode == 0, r.stdout + r.stderr
+    simkit.build("far_sim_san")
     model, where = far_model.far_with_copies(SEED)
     d = tmp_path_factory.mktemp("far")
     blob, head, zones = b"", [f"M {N}"], []
@@ -48,7 +44,7 @@ def run(far, lines, inside):
         assert any(a <= o and o + l <= e for a, e in far["zones"]), (o, l)
     cases = far["dir"] / "cases.txt"
     cases.write_text("\n".join(far["head"] + lines) + "\n")
-    r = subprocess.run([SIM, str(far["dir"] / "islands.bin"), str(cases)], capture_output=True, text=True, timeout=600)
+    r = simkit.sh([SIM, far["dir"] / "islands.bin", cases], 600)
     if r.returncode == 4:
         pytest.skip(r.stdout.strip())
     assert r.returncode == 0 and r.stdout.endswith("far_sim: OK\n"), r.stdout[-2000:] + r.stderr[-2000:]

@@ -9,16 +9,13 @@ import hashlib
 import json
 import os
 import re
-import subprocess
-from concurrent.futures import ThreadPoolExecutor
 
 import pytest
 
 from nlzm_amd import corpus
-from tests import cases
+from tests import cases, simkit
 
 HERE = os.path.dirname(os.path.abspath(__file__))
-SIM = os.path.join(HERE, "host_sim", "sim2")
 WORKERS = max(1, min(6, (os.cpu_count() or 2) - 2))
 
 # key -> (input maker (None: this machine cannot make it), simulator arguments behind the file, environment, timeout in s); in the order the runs are started
@@ -81,29 +78,24 @@ for _seed, _w, _l, _env in SPLICE:
 
 @pytest.fixture(scope="module")
 def runs(tmp_path_factory):
-    subprocess.run(["make", "-C", os.path.join(HERE, "host_sim")], check=True, capture_output=True)
+    sim, = simkit.build("sim2")
     d = tmp_path_factory.mktemp("sim_inputs")
-    ex = ThreadPoolExecutor(WORKERS)
-    futs = {}
+    runs = simkit.Runs(WORKERS)
     for n, (key, (make, args, env, timeout)) in enumerate(JOBS.items()):
         data = make()
         if data is None:
-            futs[key] = None
             continue
         p = d / f"{n}.bin"
         data.tofile(p)
-        futs[key] = ex.submit(subprocess.run, [SIM, str(p)] + args, capture_output=True, text=True, timeout=timeout, env=dict(os.environ, **env))
-    yield futs
-    ex.shutdown(wait=False, cancel_futures=True)
+        runs.submit(key, [sim, p] + args, env, timeout)
+    yield runs
+    runs.close()
 
 
 def ok(runs, key):
-    f = runs[key]
-    if f is None:
+    if key not in runs.futs:
         pytest.skip("this machine's files are not the ones the fixture was made from")
-    r = f.result()
-    assert r.returncode == 0 and ": OK" in r.stdout, r.stdout[-2000:] + r.stderr[-2000:]
-    return r
+    return runs.ok(key, ": OK")
 
 
 @pytest.mark.parametrize("name,workers,launches", STAGES)

@@ -10,29 +10,25 @@ these readers have done since they were written, scanf's reading of a number inc
 beyond 64 bits reads as 2^64 - 1, a CRC beyond 32 bits loses its upper bits), where nlzm_amd.read_index* refuses both."""
 import os
 import re
-import subprocess
 
 import pytest
 
+from tests import simkit
 from tests.cli_tools import index_text
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-SIMDIR = os.path.join(HERE, "host_sim")
-SIM = os.path.join(SIMDIR, "index_sim_san")
 M = 1 << 64
 
 
 @pytest.fixture(scope="module")
 def sim():
-    r = subprocess.run(["make", "-C", SIMDIR, "-f", "index.mk"], capture_output=True, text=True)
-    assert r.returncode == 0, r.stdout + r.stderr
-    mk = open(os.path.join(SIMDIR, "index.mk")).read()
-    assert "-fsanitize=address,undefined" in mk and "nlzm_index.h" in mk
-    return SIM
+    sim, = simkit.build("index_sim_san")
+    assert "-fsanitize=address,undefined" in simkit.compiled_with("index_sim_san")
+    assert "nlzm_amd/csrc/nlzm_index.h" in simkit.compiled_from("index_sim_san")
+    return sim
 
 
 def run(sim, *args):
-    r = subprocess.run([sim] + [str(a) for a in args], capture_output=True, text=True, timeout=120)
+    r = simkit.sh([sim, *args], 120)
     assert r.returncode == 0 and "index_sim: OK" in r.stdout, r.stdout[-2000:] + r.stderr[-2000:]
     return r.stdout
 
@@ -51,12 +47,12 @@ def test_round_trip(sim):
 
 
 def test_command_line_and_harness_read_one_header():
-    csrc = os.path.join(os.path.dirname(HERE), "nlzm_amd", "csrc")
+    csrc = os.path.join(simkit.ROOT, "nlzm_amd", "csrc")
     cli = open(os.path.join(csrc, "nlzm_cli.cpp")).read()
     assert '#include "nlzm_index.h"' in cli and "index::structural(" in cli and "index::fits_file(" in cli and "index::write(" in cli
     assert "fscanf" not in cli and "NLZMIDX %u" not in cli              # (no reader or writer of its own left)
     assert "kExtractTakes{ 2, nlzm::container::kMaxBlocks, false }" in cli and "kDecodeTakes{ 3, 4096, true }" in cli      # (what index_sim.cpp restates)
-    sim = open(os.path.join(SIMDIR, "index_sim.cpp")).read()
+    sim = open(os.path.join(simkit.SIMDIR, "index_sim.cpp")).read()
     assert "kX{ 2, 65536, false }, kD{ 3, 4096, true }" in sim and "nlzm_index.h" in sim
 
 

@@ -7,27 +7,24 @@ The sweep (in the harness): random range lists against brute force over a bitmap
 their definitions; k = 1 and k = 65,536; offsets and sums that wrap 64 bits.  Here: lists written by this file, and what the errors say."""
 import os
 import re
-import subprocess
 
 import pytest
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-SIMDIR = os.path.join(HERE, "host_sim")
-SIM = os.path.join(SIMDIR, "planes_plan_sim_san")
+from tests import simkit
+
 E_ARG = -1
 
 
 @pytest.fixture(scope="module")
 def sim():
-    r = subprocess.run(["make", "-C", SIMDIR, "-f", "planes_plan.mk"], capture_output=True, text=True)
-    assert r.returncode == 0, r.stdout + r.stderr
-    mk = open(os.path.join(SIMDIR, "planes_plan.mk")).read()
-    assert "-fsanitize=address,undefined" in mk and "nlzm_planes_plan.h" in mk
-    return SIM
+    sim, = simkit.build("planes_plan_sim_san")
+    assert "-fsanitize=address,undefined" in simkit.compiled_with("planes_plan_sim_san")
+    assert "nlzm_amd/csrc/nlzm_planes_plan.h" in simkit.compiled_from("planes_plan_sim_san")
+    return sim
 
 
 def run(sim, *args):
-    r = subprocess.run([sim] + [str(a) for a in args], capture_output=True, text=True, timeout=600)
+    r = simkit.sh([sim, *args], 600)
     assert r.returncode == 0 and "planes_plan_sim: OK" in r.stdout, r.stdout[-2000:] + r.stderr[-2000:]
     return r.stdout
 
@@ -42,13 +39,13 @@ def test_sweep(sim):
 
 
 def test_library_and_harnesses_read_one_header():
-    csrc = os.path.join(os.path.dirname(HERE), "nlzm_amd", "csrc")
+    csrc = os.path.join(simkit.ROOT, "nlzm_amd", "csrc")
     host = open(os.path.join(csrc, "nlzm_hip_planes.cpp")).read()
     assert '#include "nlzm_planes_plan.h"' in host
     for name in ("planes::check_ranges(", "planes::check_elems(", "planes::check_typed_ranges(", "planes::Table", "planes::Layout", "planes::runs("):
         assert name in host, name
     assert "runs over" not in host                  # (the typed calls' range check is the plan's, not a copy in the host file)
-    harness = open(os.path.join(SIMDIR, "planes_plan_sim.cpp")).read()
+    harness = open(os.path.join(simkit.SIMDIR, "planes_plan_sim.cpp")).read()
     for name in ("planes::check_ranges(", "planes::check_typed_ranges(", "planes::Table", "planes::Layout", "planes::runs("):
         assert name in harness, name
     plan = open(os.path.join(csrc, "nlzm_planes_plan.h")).read()

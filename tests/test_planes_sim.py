@@ -5,34 +5,27 @@ Every source lies in a mapping of its own between two PROT_NONE pages -- at the 
 flush against the page behind --, so a read outside a range that leaves the mapping ends the harness; every destination lies between guard bytes
 that have to stay as they were; LDS starts poisoned.  Up to eight ranges share a launch, and the case list is dealt to eight harness processes."""
 import os
-import subprocess
 import zlib
 from concurrent.futures import ThreadPoolExecutor
+from functools import partial
 
 import numpy as np
 import pytest
 
 from nlzm_amd import corpus
-from tests import planes_model
+from tests import planes_model, simkit
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-SIMDIR = os.path.join(HERE, "host_sim")
-SIM = os.path.join(SIMDIR, "planes_sim_san")
+SIM = os.path.join(simkit.SIMDIR, "planes_sim_san")
 SHARDS = 8
 ELEMS = planes_model.ELEMS
-
-
-def sh(cmd, timeout=900):
-    env = dict(os.environ, NLZM_SIM_POISON="7")
-    return subprocess.run([str(c) for c in cmd], capture_output=True, text=True, timeout=timeout, env=env)
+sh = partial(simkit.sh, timeout=900, env={"NLZM_SIM_POISON": "7"})
 
 
 @pytest.fixture(scope="module")
 def sim(tmp_path_factory):
-    r = subprocess.run(["make", "-C", SIMDIR, "-f", "planes.mk"], capture_output=True, text=True)
-    assert r.returncode == 0, r.stdout + r.stderr
-    mk = open(os.path.join(SIMDIR, "planes.mk")).read()
-    assert "-fsanitize=undefined" in mk and "nlzm_planes.h" in mk
+    simkit.build("planes_sim_san")
+    assert "-fsanitize=undefined" in simkit.compiled_with("planes_sim_san")
+    assert "nlzm_amd/csrc/nlzm_planes.h" in simkit.compiled_from("planes_sim_san")
     d = tmp_path_factory.mktemp("planes_sim")
     (d / "g.txt").write_text("G\n")
     (d / "none.bin").write_bytes(b"")

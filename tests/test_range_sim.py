@@ -13,27 +13,19 @@ first, and every test takes the results of its own runs: 33 s on eight cores fro
 240 s of CPU time in all), measured with nothing else running."""
 import os
 import re
-import subprocess
-from concurrent.futures import ThreadPoolExecutor
 
 import numpy as np
 import pytest
 
-from tests import cases, oracle_py
+from tests import cases, oracle_py, simkit
+from tests.simkit import sh
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-SIMDIR = os.path.join(HERE, "host_sim")
-SIM, SIM_TINY = (os.path.join(SIMDIR, n) for n in ("range_sim", "range_sim_tiny"))
 WORKERS = max(1, min(8, os.cpu_count() or 2))
 GATHER_SHARDS = 4
 
 
 def case_of(name):
     return next(c for c in cases.CASES if c[0] == name)
-
-
-def sh(cmd, timeout=900):
-    return subprocess.run([str(c) for c in cmd], capture_output=True, text=True, timeout=timeout)
 
 
 def caps_of(name, raw):
@@ -53,8 +45,7 @@ PREFIX_RUNS = [("tiny", "chunk_plus1", 8), ("tiny", "under_2k", 3), ("norm", "un
 
 @pytest.fixture(scope="module")
 def runs(tmp_path_factory):
-    r = subprocess.run(["make", "-j2", "-C", SIMDIR, "-f", "range.mk"], capture_output=True, text=True)
-    assert r.returncode == 0, r.stdout + r.stderr
+    SIM, SIM_TINY = simkit.build("range_sim", "range_sim_tiny", jobs=2)
     d = tmp_path_factory.mktemp("range_sim")
     raws = {}
     for n in sorted({n for _, n, _ in PREFIX_RUNS}):
@@ -62,7 +53,7 @@ def runs(tmp_path_factory):
         raws[n] = int(data.size)
         (d / f"{n}.nlzm").write_bytes(oracle_py.compress(data, case_of(n)[4]))
     (d / "g.txt").write_text("G\n")
-    G = int(sh([SIM, "gather", d / "g.txt"]).stdout.split()[0])
+    G = int(sh([SIM, "gather", d / "g.txt"], 900).stdout.split()[0])
     jobs, caps = [], {}
     for build, n, parts in PREFIX_RUNS:
         caps[n] = caps_of(n, raws[n])
@@ -81,16 +72,15 @@ def runs(tmp_path_factory):
     f.write_text("M 11 300\nM 12 300\nM 13 0\n")
     jobs.append((("mixed",), [SIM, "gather", f]))
     jobs.append((("plan",), [SIM, "plan"]))
-    ex = ThreadPoolExecutor(WORKERS)
-    futs = {key: ex.submit(sh, cmd) for key, cmd in jobs}
-    yield {"futs": futs, "raws": raws, "caps": caps, "G": G}
-    ex.shutdown(wait=False, cancel_futures=True)
+    started = simkit.Runs(WORKERS)
+    for key, cmd in jobs:
+        started.submit(key, cmd, timeout=900)
+    yield {"runs": started, "raws": raws, "caps": caps, "G": G}
+    started.close()
 
 
 def ok(runs, key):
-    r = runs["futs"][key].result()
-    assert r.returncode == 0 and "range_sim: OK" in r.stdout, r.stdout[-1500:] + r.stderr[-1500:]      # (-11: an access left a buffer)
-    return r.stdout
+    return runs["runs"].ok(key, "range_sim: OK").stdout      # (-11: an access left a buffer)
 
 
 def prefix_rows(runs, build, name):

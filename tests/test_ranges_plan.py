@@ -7,16 +7,12 @@ also where off + len wraps, refused and named; a bound sum that would wrap.  Her
 partition's ranges, which give the sets make_plan gives."""
 import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
 
 from nlzm_amd import corpus
-
-HERE = os.path.dirname(os.path.abspath(__file__))
-SIMDIR = os.path.join(HERE, "host_sim")
-SIM = os.path.join(SIMDIR, "ranges_plan_sim_san")
+from tests import simkit
 
 
 def bound(n):
@@ -25,15 +21,14 @@ def bound(n):
 
 @pytest.fixture(scope="module")
 def sim():
-    r = subprocess.run(["make", "-C", SIMDIR, "-f", "ranges_plan.mk"], capture_output=True, text=True)
-    assert r.returncode == 0, r.stdout + r.stderr
-    mk = open(os.path.join(SIMDIR, "ranges_plan.mk")).read()
-    assert "-fsanitize=address,undefined" in mk and "nlzm_container_plan.h" in mk
-    return SIM
+    sim, = simkit.build("ranges_plan_sim_san")
+    assert "-fsanitize=address,undefined" in simkit.compiled_with("ranges_plan_sim_san")
+    assert "nlzm_amd/csrc/nlzm_container_plan.h" in simkit.compiled_from("ranges_plan_sim_san")
+    return sim
 
 
 def run(sim, *args):
-    r = subprocess.run([sim] + [str(a) for a in args], capture_output=True, text=True, timeout=600)
+    r = simkit.sh([sim, *args], 600)
     assert r.returncode == 0 and "ranges_plan_sim: OK" in r.stdout, r.stdout[-2000:] + r.stderr[-2000:]
     return r.stdout
 
@@ -49,10 +44,10 @@ def test_sweep(sim):
 
 
 def test_library_and_harness_read_one_header():
-    csrc = os.path.join(os.path.dirname(HERE), "nlzm_amd", "csrc")
+    csrc = os.path.join(simkit.ROOT, "nlzm_amd", "csrc")
     blocks = open(os.path.join(csrc, "nlzm_hip_blocks.cpp")).read()
     assert '#include "nlzm_container_plan.h"' in blocks and "container::make_ranges_plan(" in blocks
-    assert "make_ranges_plan(" in open(os.path.join(SIMDIR, "ranges_plan_sim.cpp")).read()
+    assert "make_ranges_plan(" in open(os.path.join(simkit.SIMDIR, "ranges_plan_sim.cpp")).read()
 
 
 def test_sets_of_random_ranges(sim, tmp_path):

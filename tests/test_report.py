@@ -6,27 +6,24 @@ The golden files are what the report code printed BEFORE the slots had names: th
 acct lines and error format, pasted into a scratch harness and run on the same structs.  A swapped pair of slot names, a run's width off
 by one or a hot_class column off by one changes a line here, and the test names it."""
 import os
-import subprocess
 
 import pytest
 
+from tests import simkit
+
 HERE = os.path.dirname(os.path.abspath(__file__))
-SIMDIR = os.path.join(HERE, "host_sim")
-SIM = os.path.join(SIMDIR, "report_sim_san")
 
 
 @pytest.fixture(scope="module")
 def sim():
-    r = subprocess.run(["make", "-C", SIMDIR, "-f", "report.mk"], capture_output=True, text=True)
-    assert r.returncode == 0, r.stdout + r.stderr
-    return SIM
+    return simkit.build("report_sim_san")[0]
 
 
 @pytest.mark.parametrize("what", ["all", "fine", "gates", "cold", "acct", "counters", "error"])
 def test_report_text_is_unchanged(sim, what):
     """all: every slot set, hot bins on; fine: the same with small divisors, so that no two slots round to the same figure; gates: every conditional section's gate zero (then hot_steps too); cold: hot bins off;
     acct / counters / error: the block set's rows, every counter name (and an unknown one), the error text's stage part"""
-    r = subprocess.run([sim, what], capture_output=True, text=True, timeout=60)
+    r = simkit.sh([sim, what], 60)
     assert r.returncode == 0, r.stdout + r.stderr
     want = open(os.path.join(HERE, "golden", f"report_{what}.txt")).read()
     got_lines, want_lines = r.stdout.splitlines(), want.splitlines()

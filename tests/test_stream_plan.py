@@ -7,27 +7,24 @@ like the first, so depth 2 needs room for two uncut launches -- and a stream of 
 every threshold: 1,000 bytes per chunk, launches of 10 chunks."""
 import os
 import re
-import subprocess
 
 import pytest
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-SIMDIR = os.path.join(HERE, "host_sim")
-SIM = os.path.join(SIMDIR, "stream_plan_sim_san")
+from tests import simkit
+
 PER_CHUNK, BATCH, NCHUNKS = 1000, 10, 100
 
 
 @pytest.fixture(scope="module")
 def sim():
-    r = subprocess.run(["make", "-C", SIMDIR, "-f", "stream_plan.mk"], capture_output=True, text=True)
-    assert r.returncode == 0, r.stdout + r.stderr
-    mk = open(os.path.join(SIMDIR, "stream_plan.mk")).read()
-    assert "-fsanitize=address,undefined" in mk and "nlzm_stream_plan.h" in mk
-    return SIM
+    sim, = simkit.build("stream_plan_sim_san")
+    assert "-fsanitize=address,undefined" in simkit.compiled_with("stream_plan_sim_san")
+    assert "nlzm_amd/csrc/nlzm_stream_plan.h" in simkit.compiled_from("stream_plan_sim_san")
+    return sim
 
 
 def plan(sim, free, table=0, per_chunk=PER_CHUNK, batch=BATCH, nchunks=NCHUNKS):
-    r = subprocess.run([sim, "plan"] + [str(a) for a in (free, table, per_chunk, batch, nchunks)], capture_output=True, text=True, timeout=60)
+    r = simkit.sh([sim, "plan", free, table, per_chunk, batch, nchunks], 60)
     assert r.returncode == 0 and "stream_plan_sim: OK" in r.stdout, r.stdout[-2000:] + r.stderr[-2000:]
     m = re.search(r"^plan (\d+) (\d+)$", r.stdout, re.M)
     return int(m.group(1)), int(m.group(2))
@@ -62,9 +59,9 @@ def test_a_stream_of_one_launch_has_one_set(sim):
 
 
 def test_library_and_harness_read_one_header():
-    csrc = os.path.join(os.path.dirname(HERE), "nlzm_amd", "csrc")
+    csrc = os.path.join(simkit.ROOT, "nlzm_amd", "csrc")
     assert '#include "nlzm_stream_plan.h"' in open(os.path.join(csrc, "nlzm_hip.cpp")).read()
     assert "stream_plan::make_plan(" in open(os.path.join(csrc, "nlzm_hip.cpp")).read()
-    assert "nlzm_stream_plan.h" in open(os.path.join(SIMDIR, "stream_plan_sim.cpp")).read()
+    assert "nlzm_stream_plan.h" in open(os.path.join(simkit.SIMDIR, "stream_plan_sim.cpp")).read()
     text = open(os.path.join(csrc, "nlzm_stream_plan.h")).read()
     assert "hip" not in text.lower().replace("nlzm_hip", "")          # no device in it

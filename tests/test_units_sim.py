@@ -3,33 +3,30 @@ the one implementation the gather role, the CRC's segments, the equal-range find
 harness (tests/host_sim/units_sim.cpp) is a program of its own under AddressSanitizer and UBSan and includes the header the library includes; every
 number it prints is held to Python's own integers and to bisect."""
 import os
-import subprocess
 from bisect import bisect_right
 
 import pytest
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-SIMDIR = os.path.join(HERE, "host_sim")
-SIM = os.path.join(SIMDIR, "units_sim_san")
-CSRC = os.path.join(os.path.dirname(HERE), "nlzm_amd", "csrc")
+from tests import simkit
+
+CSRC = os.path.join(simkit.ROOT, "nlzm_amd", "csrc")
 G4 = 1 << 32
 UNITS = (32768, 65536, 1)
 
 
 @pytest.fixture(scope="module")
 def sim():
-    r = subprocess.run(["make", "-C", SIMDIR, "-f", "units.mk"], capture_output=True, text=True)
-    assert r.returncode == 0, r.stdout + r.stderr
-    mk = open(os.path.join(SIMDIR, "units.mk")).read()
-    assert "-fsanitize=address,undefined" in mk and "nlzm_units.h" in mk
-    return SIM
+    sim, = simkit.build("units_sim_san")
+    assert "-fsanitize=address,undefined" in simkit.compiled_with("units_sim_san")
+    assert "nlzm_amd/csrc/nlzm_units.h" in simkit.compiled_from("units_sim_san")
+    return sim
 
 
 def run(sim, tmp_path, lines):
     """one output line per case line: lists of integers"""
     path = tmp_path / "cases.txt"
     path.write_text("".join(line + "\n" for line in lines))
-    r = subprocess.run([sim, str(path)], capture_output=True, text=True, timeout=60)
+    r = simkit.sh([sim, path], 60)
     assert r.returncode == 0 and r.stdout.endswith("units_sim: OK\n"), r.stdout[-2000:] + r.stderr[-2000:]
     out = r.stdout.splitlines()[:-1]
     assert len(out) == len(lines)
@@ -124,10 +121,12 @@ def test_blocks_for(sim, tmp_path):
 
 
 def test_one_definition():
-    """the role headers hold no owner search and no pointer cast of their own"""
-    for name in ("nlzm_range.h", "nlzm_crc.h", "nlzm_planes.h", "nlzm_dedup.h"):
+    """the role headers hold no owner search and no pointer cast of their own, and the program that runs each role on the CPU was compiled
+    from the shared table"""
+    for name, program in (("nlzm_range.h", "range_sim"), ("nlzm_crc.h", "crc_sim_san"), ("nlzm_planes.h", "planes_sim_san"), ("nlzm_dedup.h", "dedup_sim_san")):
         text = open(os.path.join(CSRC, name)).read()
         assert "while (hi - lo > 1)" not in text and "units::owner_of(" in text and '#include "nlzm_units.h"' in text, name
+        assert {"nlzm_amd/csrc/nlzm_units.h", "nlzm_amd/csrc/" + name} <= simkit.compiled_from(program), program
     assert open(os.path.join(CSRC, "nlzm_units.h")).read().count("while (hi - lo > 1)") == 1
     for name in sorted(os.listdir(CSRC)):
         if name.endswith((".h", ".hip", ".cpp")) and name not in ("nlzm_units.h", "nlzm_kernels.hip", "xw.h"):

@@ -3,28 +3,24 @@
 checked from both sides.  Also here: the checker's own test (a table with one word altered must fail, and name the word), and the
 simulator's refusal to hand a live lane the value of a lane that has left the role.  2 s, nearly all of it the harness's build."""
 import os
-import subprocess
 
 import numpy as np
 import pytest
 
+from tests import simkit
 from tests import xw_model as xm
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-SIMDIR = os.path.join(HERE, "host_sim")
-SIM = os.path.join(SIMDIR, "xw_probe_sim_san")
+SIM = os.path.join(simkit.SIMDIR, "xw_probe_sim_san")
 
 
 def run_sim(d, table, tag):
     table.input().tofile(d / f"in_{tag}.bin")
-    r = subprocess.run([SIM, str(d / f"in_{tag}.bin"), str(d / f"out0_{tag}.bin"), str(d / f"out1_{tag}.bin")], capture_output=True, text=True, timeout=300)
-    return r
+    return simkit.sh([SIM, d / f"in_{tag}.bin", d / f"out0_{tag}.bin", d / f"out1_{tag}.bin"], 300)
 
 
 @pytest.fixture(scope="module")
 def sim(tmp_path_factory):
-    r = subprocess.run(["make", "-C", SIMDIR, "-f", "probe.mk"], capture_output=True, text=True)
-    assert r.returncode == 0, r.stdout + r.stderr
+    simkit.build("xw_probe_sim_san")
     d = tmp_path_factory.mktemp("xw_probe")
     T = xm.Table(strict=True)
     r = run_sim(d, T, "strict")
