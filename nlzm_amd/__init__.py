@@ -4,6 +4,7 @@ The product is the C-ABI shared library ``libnlzm_hip.so`` (include/nlzm_hip.h) 
 ``nlzm`` command line built from ``nlzm_amd/csrc``.  This module is the thin ctypes
 binding the tests and ``bench.py`` use; it adds no algorithmic code and has no CPU
 fallback: every call below fails loudly if the library or a gfx950 device is missing.
+The signatures are the table in ``_abi.py``; the sidecar index reader is ``index.py``.
 """
 from __future__ import annotations
 
@@ -17,56 +18,19 @@ import numpy as np
 # them (only effective if the runtime has not started yet)
 os.environ.setdefault("GPU_MAX_HW_QUEUES", "16")
 
+from ._abi import ABI_SYMBOLS, Stats, Timing, bind                    # noqa: E402,F401  (re-exported)
+from .index import read_index, read_index_typed                        # noqa: E402,F401  (re-exported)
+
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("NLZM_LIB", os.path.join(_HERE, "libnlzm_hip.so"))     # override: diagnostic builds only
 CLI_PATH = os.path.join(_HERE, "nlzm")
 
-# every symbol include/nlzm_hip.h declares
-ABI_SYMBOLS = [
-    "nlzm_hip_init", "nlzm_hip_shutdown", "nlzm_hip_last_error", "nlzm_hip_compress_bound",
-    "nlzm_hip_geometry", "nlzm_hip_compress", "nlzm_hip_compress_dev", "nlzm_hip_stream_begin",
-    "nlzm_hip_stream_step", "nlzm_hip_stream_finish", "nlzm_hip_get_stats", "nlzm_hip_get_timing",
-    "nlzm_hip_rans_frames", "nlzm_hip_find_matches", "nlzm_hip_parse_emit", "nlzm_hip_set_option",
-    "nlzm_hip_blocks_begin", "nlzm_hip_blocks_step", "nlzm_hip_blocks_finish", "nlzm_hip_blocks_abandon",
-    "nlzm_hip_compress_blocks_dev", "nlzm_hip_compress_blocks", "nlzm_hip_compress_blocks_multi", "nlzm_hip_compress_blocks_bound",
-    "nlzm_hip_feed_begin", "nlzm_hip_feed", "nlzm_hip_feed_output", "nlzm_hip_feed_finish", "nlzm_hip_feed_end",
-    "nlzm_hip_block_placement", "nlzm_hip_get_counter",
-    "nlzm_hip_decompress_dev", "nlzm_hip_decompress", "nlzm_hip_decompress_blocks_dev", "nlzm_hip_decompress_blocks", "nlzm_hip_verify_dev", "nlzm_hip_verify",
-    "nlzm_hip_crc32_dev", "nlzm_hip_crc32", "nlzm_hip_crc32_ranges_dev", "nlzm_hip_crc32_ranges", "nlzm_hip_crc32_combine", "nlzm_hip_feed_input_crc32",
-    "nlzm_hip_check_dev", "nlzm_hip_check",
-    "nlzm_hip_read_ranges_dev", "nlzm_hip_read_ranges",
-    "nlzm_hip_decode_begin_dev", "nlzm_hip_decode_begin", "nlzm_hip_decode_step", "nlzm_hip_decode_extend_dev", "nlzm_hip_decode_fetch",
-    "nlzm_hip_decode_finish", "nlzm_hip_decode_abandon",
-    "nlzm_hip_compress_ranges_dev", "nlzm_hip_compress_ranges", "nlzm_hip_compress_ranges_bound", "nlzm_hip_cut_points_dev", "nlzm_hip_cut_points",
-    "nlzm_hip_equal_ranges_dev", "nlzm_hip_equal_ranges",
-    "nlzm_hip_planes_dev", "nlzm_hip_planes", "nlzm_hip_compress_ranges_typed_dev", "nlzm_hip_compress_ranges_typed",
-    "nlzm_hip_decompress_blocks_typed_dev", "nlzm_hip_decompress_blocks_typed",
-]
 DECODE_MORE = 1          # NLZM_HIP_DECODE_MORE
 TO_THE_END = (1 << 64) - 1
 
 
 class NlzmError(RuntimeError):
     pass
-
-
-class Stats(C.Structure):
-    _fields_ = [(n, C.c_uint64) for n in (
-        "in_bytes", "out_bytes", "bt_calls", "bt_tests", "cmp_bytes", "ht_rows", "rk_probes", "rk_inserts",
-        "positions", "nice_positions", "segments", "n_literal", "n_dict", "n_rep", "rans_syms", "bit_ops",
-        "frames", "shifts", "uncertain_positions")]
-
-    def as_dict(self):
-        return {n: int(getattr(self, n)) for n, _ in self._fields_}
-
-
-class Timing(C.Structure):
-    _fields_ = [("total_ms", C.c_double), ("h2d_ms", C.c_double), ("d2h_ms", C.c_double), ("prep_ms", C.c_double),
-                ("match_parse_ms", C.c_double), ("rans_ms", C.c_double), ("match_parse_launches", C.c_uint32),
-                ("rans_launches", C.c_uint32), ("prep_launches", C.c_uint32)]
-
-    def as_dict(self):
-        return {n: getattr(self, n) for n, _ in self._fields_}
 
 
 def build(force: bool = False) -> None:
@@ -82,102 +46,83 @@ _lib = None
 
 
 def load_library() -> C.CDLL:
-    """dlopen the in-tree library (no device needed just to load it)."""
+    """dlopen the in-tree library (no device needed just to load it) and give it the signatures of _abi.TABLE."""
     global _lib
-    if _lib is not None:
-        return _lib
-    if not os.path.exists(LIB_PATH):
-        raise NlzmError(f"{LIB_PATH} is missing: run `python -c 'import __graft_entry__ as g; g.build()'` "
-                        "(there is no CPU fallback)")
-    lib = C.CDLL(LIB_PATH)
-    u8p, u32p, u64p = C.POINTER(C.c_uint8), C.POINTER(C.c_uint32), C.POINTER(C.c_uint64)
-    lib.nlzm_hip_init.argtypes = [C.c_int]
-    lib.nlzm_hip_last_error.restype = C.c_char_p
-    lib.nlzm_hip_compress_bound.argtypes = [C.c_uint64]
-    lib.nlzm_hip_compress_bound.restype = C.c_uint64
-    lib.nlzm_hip_geometry.argtypes = [C.c_uint64, C.c_uint32, u32p, u32p, u32p, u32p]
-    lib.nlzm_hip_geometry.restype = None
-    lib.nlzm_hip_compress.argtypes = [C.c_void_p, C.c_uint64, C.c_uint32, C.c_void_p, C.c_uint64, u64p]
-    lib.nlzm_hip_compress_dev.argtypes = [C.c_void_p, C.c_uint64, C.c_uint32, C.c_void_p, C.c_uint64, u64p]
-    lib.nlzm_hip_stream_begin.argtypes = [C.c_void_p, C.c_uint64, C.c_uint32, C.c_void_p, C.c_uint64]
-    lib.nlzm_hip_stream_step.argtypes = [C.c_uint32, u64p, u64p, C.POINTER(C.c_int)]
-    lib.nlzm_hip_stream_finish.argtypes = [u64p]
-    lib.nlzm_hip_get_stats.argtypes = [C.POINTER(Stats)]
-    lib.nlzm_hip_get_timing.argtypes = [C.POINTER(Timing)]
-    if hasattr(lib, "nlzm_hip_get_counter"):       # (absent from older diagnostic builds loaded through NLZM_LIB)
-        lib.nlzm_hip_get_counter.argtypes = [C.c_char_p, u64p]
-    lib.nlzm_hip_rans_frames.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32,
-                                         C.c_void_p, C.c_uint64, C.c_void_p]
-    lib.nlzm_hip_find_matches.argtypes = [C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint64, C.c_uint64, C.c_void_p,
-                                          C.c_uint64, u64p]
-    lib.nlzm_hip_parse_emit.argtypes = [C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint32,
-                                        C.c_void_p, C.c_uint32, C.c_void_p]
-    lib.nlzm_hip_set_option.argtypes = [C.c_char_p, C.c_int64]
-    lib.nlzm_hip_blocks_begin.argtypes = [C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint32]
-    lib.nlzm_hip_blocks_step.argtypes = [C.c_uint32, u64p, C.POINTER(C.c_int), C.POINTER(C.c_double)]
-    lib.nlzm_hip_blocks_finish.argtypes = [C.c_void_p, C.c_uint64, u64p, u64p]
-    lib.nlzm_hip_blocks_abandon.restype = None
-    if hasattr(lib, "nlzm_hip_compress_blocks_bound"):     # (absent from older diagnostic builds loaded through NLZM_LIB)
-        lib.nlzm_hip_compress_blocks_bound.argtypes = [C.c_uint64, C.c_uint32]
-        lib.nlzm_hip_compress_blocks_bound.restype = C.c_uint64
-    lib.nlzm_hip_compress_blocks.argtypes = [C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint64, u64p, u64p]
-    lib.nlzm_hip_feed_begin.argtypes = [C.c_uint64, C.c_uint32]
-    lib.nlzm_hip_feed.argtypes = [C.c_void_p, C.c_uint64]
-    lib.nlzm_hip_feed_output.argtypes = [C.c_void_p, C.c_uint64, u64p]
-    lib.nlzm_hip_feed_end.restype = None
-    lib.nlzm_hip_compress_blocks_multi.argtypes = [C.POINTER(C.c_int), C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint64, C.c_uint32,
-                                                   C.c_void_p, C.c_uint64, u64p, u64p]
-    lib.nlzm_hip_compress_blocks_dev.argtypes = [C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint64, u64p, u64p]
-    lib.nlzm_hip_decompress_dev.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, u64p]
-    lib.nlzm_hip_decompress.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, u64p]
-    lib.nlzm_hip_decompress_blocks_dev.argtypes = [C.c_void_p, C.c_uint64, C.c_uint32, u64p, u64p, C.c_void_p, C.c_uint64, u64p, u64p]
-    lib.nlzm_hip_decompress_blocks.argtypes = [C.c_void_p, C.c_uint64, C.c_uint32, u64p, u64p, C.c_void_p, C.c_uint64, u64p, u64p]
-    lib.nlzm_hip_verify_dev.argtypes = [C.c_void_p, C.c_uint64, C.c_uint32, u64p, C.c_void_p, C.c_uint64, u64p, u64p]
-    lib.nlzm_hip_verify.argtypes = [C.c_void_p, C.c_uint64, C.c_uint32, u64p, C.c_void_p, C.c_uint64, u64p, u64p]
-    lib.nlzm_hip_crc32_dev.argtypes = [C.c_void_p, C.c_uint64, C.c_uint32, u32p]
-    lib.nlzm_hip_crc32.argtypes = [C.c_void_p, C.c_uint64, C.c_uint32, u32p]
-    lib.nlzm_hip_crc32_ranges_dev.argtypes = [C.c_void_p, C.c_uint64, C.c_uint32, u64p, u64p, u32p]
-    lib.nlzm_hip_crc32_ranges.argtypes = [C.c_void_p, C.c_uint64, C.c_uint32, u64p, u64p, u32p]
-    lib.nlzm_hip_crc32_combine.argtypes = [C.c_uint32, C.c_uint32, C.c_uint64]
-    lib.nlzm_hip_crc32_combine.restype = C.c_uint32
-    lib.nlzm_hip_feed_input_crc32.argtypes = [u32p]
-    lib.nlzm_hip_check_dev.argtypes = [C.c_void_p, C.c_uint64, C.c_uint32, u64p, u64p, u32p, u32p, u32p]
-    lib.nlzm_hip_check.argtypes = [C.c_void_p, C.c_uint64, C.c_uint32, u64p, u64p, u32p, u32p, u32p]
-    lib.nlzm_hip_read_ranges_dev.argtypes = [C.c_void_p, C.c_uint64, C.c_uint32, u64p, u64p, u32p, C.c_uint32, u64p, u64p, C.c_void_p, C.c_uint64, u64p, u32p]
-    lib.nlzm_hip_read_ranges.argtypes = [C.c_void_p, C.c_uint64, C.c_uint32, u64p, u64p, u32p, C.c_uint32, u64p, u64p, C.c_void_p, C.c_uint64, u64p, u32p]
-    if hasattr(lib, "nlzm_hip_decode_begin"):      # (absent from older diagnostic builds loaded through NLZM_LIB)
-        lib.nlzm_hip_decode_begin_dev.argtypes = [C.c_void_p, C.c_uint64, C.c_uint32, u64p, u64p, C.c_void_p, C.c_uint64, C.c_uint32]
-        lib.nlzm_hip_decode_begin.argtypes = [C.c_void_p, C.c_uint64, C.c_uint32, u64p, u64p, C.c_uint32]
-        lib.nlzm_hip_decode_step.argtypes = [C.c_uint32, u64p, u64p, C.POINTER(C.c_int), C.POINTER(C.c_double)]
-        lib.nlzm_hip_decode_extend_dev.argtypes = [C.c_uint64]
-        lib.nlzm_hip_decode_fetch.argtypes = [C.c_uint64, C.c_uint64, C.c_void_p]
-        lib.nlzm_hip_decode_finish.argtypes = [u64p, u64p]
-        lib.nlzm_hip_decode_abandon.restype = None
-    if hasattr(lib, "nlzm_hip_compress_ranges"):   # (absent from older diagnostic builds loaded through NLZM_LIB)
-        lib.nlzm_hip_compress_ranges_dev.argtypes = [C.c_void_p, C.c_uint64, C.c_uint32, u64p, u64p, C.c_uint32, C.c_void_p, C.c_uint64, u64p, u64p]
-        lib.nlzm_hip_compress_ranges.argtypes = [C.c_void_p, C.c_uint64, C.c_uint32, u64p, u64p, C.c_uint32, C.c_void_p, C.c_uint64, u64p, u64p]
-        lib.nlzm_hip_compress_ranges_bound.argtypes = [C.c_uint32, u64p]
-        lib.nlzm_hip_compress_ranges_bound.restype = C.c_uint64
-        lib.nlzm_hip_cut_points_dev.argtypes = [C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint64, C.c_uint64, u64p, C.c_uint32, u32p]
-        lib.nlzm_hip_cut_points.argtypes = [C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint64, C.c_uint64, u64p, C.c_uint32, u32p]
-    if hasattr(lib, "nlzm_hip_equal_ranges"):      # (absent from older diagnostic builds loaded through NLZM_LIB)
-        lib.nlzm_hip_equal_ranges_dev.argtypes = [C.c_void_p, C.c_uint64, C.c_uint32, u64p, u64p, u32p, u64p]
-        lib.nlzm_hip_equal_ranges.argtypes = [C.c_void_p, C.c_uint64, C.c_uint32, u64p, u64p, u32p, u64p]
-    if hasattr(lib, "nlzm_hip_planes"):            # (absent from older diagnostic builds loaded through NLZM_LIB)
-        lib.nlzm_hip_planes_dev.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_uint32, u64p, u64p, u64p, u8p, C.c_int]
-        lib.nlzm_hip_planes.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_uint32, u64p, u64p, u64p, u8p, C.c_int]
-        lib.nlzm_hip_compress_ranges_typed_dev.argtypes = [C.c_void_p, C.c_uint64, C.c_uint32, u64p, u64p, u8p, C.c_uint32, C.c_void_p, C.c_uint64, u64p, u64p]
-        lib.nlzm_hip_compress_ranges_typed.argtypes = [C.c_void_p, C.c_uint64, C.c_uint32, u64p, u64p, u8p, C.c_uint32, C.c_void_p, C.c_uint64, u64p, u64p]
-        lib.nlzm_hip_decompress_blocks_typed_dev.argtypes = [C.c_void_p, C.c_uint64, C.c_uint32, u64p, u64p, u8p, C.c_void_p, C.c_uint64, u64p, u64p]
-        lib.nlzm_hip_decompress_blocks_typed.argtypes = [C.c_void_p, C.c_uint64, C.c_uint32, u64p, u64p, u8p, C.c_void_p, C.c_uint64, u64p, u64p]
-    _lib = lib
-    return lib
+    if _lib is None:
+        if not os.path.exists(LIB_PATH):
+            raise NlzmError(f"{LIB_PATH} is missing: run `python -c 'import __graft_entry__ as g; g.build()'` "
+                            "(there is no CPU fallback)")
+        _lib = bind(C.CDLL(LIB_PATH))
+    return _lib
 
 
 def _chk(rc: int) -> None:
     if rc != 0:
         raise NlzmError(f"nlzm_hip error {rc}: {load_library().nlzm_hip_last_error().decode()}")
 
+
+# ---- marshalling: what every function below hands to the library, and takes back
+
+def _bytes_in(data) -> np.ndarray:
+    return np.ascontiguousarray(np.frombuffer(data, dtype=np.uint8) if not isinstance(data, np.ndarray) else data)
+
+
+def _ptr(a: np.ndarray):
+    """the array's address, NULL when it is empty"""
+    return a.ctypes.data if a.size else None
+
+
+def _arr(ctype, values, slots: int = 0):
+    """a ctypes array of the integers `values`, `slots` entries long at least; None stays None (NULL)"""
+    if values is None:
+        return None
+    values = [int(v) for v in values]
+    return (ctype * max(slots, len(values)))(*values)
+
+
+def _ranges(ranges, slots: int = 0):
+    """(k, off[], len[]) of a list of (offset, length)"""
+    return len(ranges), _arr(C.c_uint64, [o for o, _ in ranges], slots), _arr(C.c_uint64, [l for _, l in ranges], slots)
+
+
+def _elems(elems, slots: int = 0):
+    """element sizes as bytes; one that does not fit a byte goes as 0, which the library refuses by the range's name"""
+    return None if elems is None else _arr(C.c_uint8, [int(e) if 0 <= int(e) < 256 else 0 for e in elems], slots)
+
+
+def _crcs(crcs):
+    return None if crcs is None else _arr(C.c_uint32, [int(c) & 0xFFFFFFFF for c in crcs])
+
+
+def _one_per_block(k: int, **lists) -> None:
+    for name, v in lists.items():
+        if v is not None and len(v) != k:
+            raise ValueError(f"{name}: one entry per block")
+
+
+def _cut(buf, lens, total=None, take=lambda piece: piece.tobytes()) -> list:
+    """buf cut into one piece per length, back to back; total: what the lengths must come to"""
+    out, pos = [], 0
+    for n in lens:
+        out.append(take(buf[pos: pos + int(n)]))
+        pos += int(n)
+    assert total is None or pos == total
+    return out
+
+
+def _with_dedup(dedup: bool, call):
+    """call() with option "dedup_ranges" set for its duration when dedup is true, the option as it stood afterwards"""
+    if not dedup:
+        return call()
+    was = counter("dedup_ranges")        # (the option as it stands)
+    set_option("dedup_ranges", 1)
+    try:
+        return call()
+    finally:
+        set_option("dedup_ranges", was)
+
+
+# ---- the entry points
 
 def init(device: int = 0) -> None:
     _chk(load_library().nlzm_hip_init(device))
@@ -201,12 +146,12 @@ def geometry(flen: int, hist_bits: int) -> dict:
 def compress(data, hist_bits: int = 22) -> bytes:
     """encode_file replacement on host buffers (NLZM.cpp:1711); returns the whole stream."""
     lib = load_library()
-    src = np.ascontiguousarray(np.frombuffer(data, dtype=np.uint8) if not isinstance(data, np.ndarray) else data)
+    src = _bytes_in(data)
     n = int(src.size)
     cap = int(lib.nlzm_hip_compress_bound(n))
     dst = np.empty(cap, dtype=np.uint8)
     out_len = C.c_uint64(0)
-    _chk(lib.nlzm_hip_compress(src.ctypes.data if n else None, n, hist_bits, dst.ctypes.data, cap, C.byref(out_len)))
+    _chk(lib.nlzm_hip_compress(_ptr(src), n, hist_bits, dst.ctypes.data, cap, C.byref(out_len)))
     return dst[: out_len.value].tobytes()
 
 
@@ -215,7 +160,7 @@ def compress_blocks(data, nblocks: int, hist_bits: int = 22) -> list[bytes]:
     them (64 on an MI355X), more of them in sets one after another (option "container_set_blocks"; counter "container_sets"); the reference
     equivalent is encode_file (NLZM.cpp:1711) run on each range."""
     lib = load_library()
-    src = np.ascontiguousarray(np.frombuffer(data, dtype=np.uint8) if not isinstance(data, np.ndarray) else data)
+    src = _bytes_in(data)
     n = int(src.size)
     if not 1 <= nblocks <= 65536:
         raise ValueError("nblocks: 1 to 65536")
@@ -223,13 +168,8 @@ def compress_blocks(data, nblocks: int, hist_bits: int = 22) -> list[bytes]:
     dst = np.empty(cap, dtype=np.uint8)
     lens = (C.c_uint64 * nblocks)()
     out_len = C.c_uint64(0)
-    _chk(lib.nlzm_hip_compress_blocks(src.ctypes.data if n else None, n, nblocks, hist_bits, dst.ctypes.data, cap, lens, C.byref(out_len)))
-    out, pos = [], 0
-    for i in range(nblocks):
-        out.append(dst[pos: pos + int(lens[i])].tobytes())
-        pos += int(lens[i])
-    assert pos == out_len.value
-    return out
+    _chk(lib.nlzm_hip_compress_blocks(_ptr(src), n, nblocks, hist_bits, dst.ctypes.data, cap, lens, C.byref(out_len)))
+    return _cut(dst, lens, out_len.value)
 
 
 def equal_ranges(data, ranges, fingerprints=None) -> list[int]:
@@ -238,15 +178,25 @@ def equal_ranges(data, ranges, fingerprints=None) -> list[int]:
     range's 64-bit fingerprint (the rule: tests/dedup_model.py)."""
     lib = load_library()
     src = _bytes_in(data)
-    n, k = int(src.size), len(ranges)
-    if not 1 <= k <= 65536:
+    if not 1 <= len(ranges) <= 65536:
         raise ValueError("ranges: 1 to 65536")
-    off, ln = (C.c_uint64 * k)(*[int(o) for o, _ in ranges]), (C.c_uint64 * k)(*[int(l) for _, l in ranges])
+    k, off, ln = _ranges(ranges)
     first, fp = (C.c_uint32 * k)(), (C.c_uint64 * k)()
-    _chk(lib.nlzm_hip_equal_ranges(src.ctypes.data if n else None, n, k, off, ln, first, fp))
+    _chk(lib.nlzm_hip_equal_ranges(_ptr(src), int(src.size), k, off, ln, first, fp))
     if fingerprints is not None:
         fingerprints[:] = [int(x) for x in fp]
     return [int(x) for x in first]
+
+
+def _compress_ranges(entry, src, ranges, extra: tuple, hist_bits: int, dedup: bool) -> list[bytes]:
+    """what compress_ranges and compress_typed share: `entry` is the library's function, `extra` what it takes between the lengths and the window"""
+    k, off, ln = _ranges(ranges)
+    cap = int(load_library().nlzm_hip_compress_ranges_bound(k, ln))
+    dst = np.empty(max(1, cap), dtype=np.uint8)
+    lens = (C.c_uint64 * k)()
+    out_len = C.c_uint64(0)
+    _with_dedup(dedup, lambda: _chk(entry(_ptr(src), int(src.size), k, off, ln, *extra, hist_bits, dst.ctypes.data, cap, lens, C.byref(out_len))))
+    return _cut(dst, lens, out_len.value)
 
 
 def compress_ranges(data, ranges, hist_bits: int = 22, dedup: bool = False) -> list[bytes]:
@@ -254,42 +204,13 @@ def compress_ranges(data, ranges, hist_bits: int = 22, dedup: bool = False) -> l
     is the reference's encode_file (NLZM.cpp:1711) run on data[off:off + length].  Up to a launch's capacity (64 on an MI355X) they are one block
     set, more of them run in sets of consecutive ranges (counter "container_sets").  dedup: option "dedup_ranges" for this call -- a range whose
     bytes an earlier one holds is not compressed again, its stream is a copy (the same bytes come back; the "dedup_*" counters say what was saved)."""
-    if dedup:
-        was = counter("dedup_ranges")        # (the option as it stands)
-        set_option("dedup_ranges", 1)
-        try:
-            return compress_ranges(data, ranges, hist_bits)
-        finally:
-            set_option("dedup_ranges", was)
+    if dedup:                # (the option is set before the arguments are looked at)
+        return _with_dedup(True, lambda: compress_ranges(data, ranges, hist_bits))
     lib = load_library()
     src = _bytes_in(data)
-    n, k = int(src.size), len(ranges)
-    if not 1 <= k <= 65536:
+    if not 1 <= len(ranges) <= 65536:
         raise ValueError("ranges: 1 to 65536")
-    off, ln = (C.c_uint64 * k)(*[int(o) for o, _ in ranges]), (C.c_uint64 * k)(*[int(l) for _, l in ranges])
-    cap = int(lib.nlzm_hip_compress_ranges_bound(k, ln))
-    dst = np.empty(max(1, cap), dtype=np.uint8)
-    lens = (C.c_uint64 * k)()
-    out_len = C.c_uint64(0)
-    _chk(lib.nlzm_hip_compress_ranges(src.ctypes.data if n else None, n, k, off, ln, hist_bits, dst.ctypes.data, cap, lens, C.byref(out_len)))
-    out, pos = [], 0
-    for i in range(k):
-        out.append(dst[pos: pos + int(lens[i])].tobytes())
-        pos += int(lens[i])
-    assert pos == out_len.value
-    return out
-
-
-def _with_dedup(dedup: bool, call):
-    """call() with option "dedup_ranges" set for its duration when dedup is true, the option as it stood afterwards"""
-    if not dedup:
-        return call()
-    was = counter("dedup_ranges")
-    set_option("dedup_ranges", 1)
-    try:
-        return call()
-    finally:
-        set_option("dedup_ranges", was)
+    return _compress_ranges(lib.nlzm_hip_compress_ranges, src, ranges, (), hist_bits, False)
 
 
 def planes(data, ranges, elems, inverse: bool = False) -> list[bytes]:
@@ -298,19 +219,17 @@ def planes(data, ranges, elems, inverse: bool = False) -> list[bytes]:
     inverse: the filter undone.  The ranges may be empty, overlap and repeat; one result per range."""
     lib = load_library()
     src = _bytes_in(data)
-    n, k = int(src.size), len(ranges)
-    if not 1 <= k <= 65536 or len(elems) != k:
+    if not 1 <= len(ranges) <= 65536 or len(elems) != len(ranges):
         raise ValueError("ranges: 1 to 65536, one element size each")
+    k, off, ln = _ranges(ranges)
     lens = [int(l) for _, l in ranges]
     ok = all(0 <= l < 1 << 48 for l in lens)       # (a length that cannot be: the library names the range, and nothing is written)
     at, total = [], 0
     for l in lens:
         at.append(total)
         total += l if ok else 0
-    off, ln, to = (C.c_uint64 * k)(*[int(o) for o, _ in ranges]), (C.c_uint64 * k)(*lens), (C.c_uint64 * k)(*at)
-    el = (C.c_uint8 * k)(*[int(e) if 0 <= int(e) < 256 else 0 for e in elems])
     dst = np.empty(max(1, total), dtype=np.uint8)
-    _chk(lib.nlzm_hip_planes(src.ctypes.data if n else None, n, dst.ctypes.data, total, k, off, to, ln, el, 1 if inverse else 0))
+    _chk(lib.nlzm_hip_planes(_ptr(src), int(src.size), dst.ctypes.data, total, k, off, _arr(C.c_uint64, at), ln, _elems(elems), 1 if inverse else 0))
     return [dst[a: a + l].tobytes() for a, l in zip(at, lens)]
 
 
@@ -320,23 +239,9 @@ def compress_typed(data, ranges, elems, hist_bits: int = 22, dedup: bool = False
     elems None: compress_ranges itself."""
     lib = load_library()
     src = _bytes_in(data)
-    n, k = int(src.size), len(ranges)
-    if not 1 <= k <= 65536 or (elems is not None and len(elems) != k):
+    if not 1 <= len(ranges) <= 65536 or (elems is not None and len(elems) != len(ranges)):
         raise ValueError("ranges: 1 to 65536, one element size each")
-    off, ln = (C.c_uint64 * k)(*[int(o) for o, _ in ranges]), (C.c_uint64 * k)(*[int(l) for _, l in ranges])
-    el = (C.c_uint8 * k)(*[int(e) if 0 <= int(e) < 256 else 0 for e in elems]) if elems is not None else None
-    cap = int(lib.nlzm_hip_compress_ranges_bound(k, ln))
-    dst = np.empty(max(1, cap), dtype=np.uint8)
-    lens = (C.c_uint64 * k)()
-    out_len = C.c_uint64(0)
-    _with_dedup(dedup, lambda: _chk(lib.nlzm_hip_compress_ranges_typed(src.ctypes.data if n else None, n, k, off, ln, el, hist_bits, dst.ctypes.data, cap, lens,
-                                                                        C.byref(out_len))))
-    out, pos = [], 0
-    for i in range(k):
-        out.append(dst[pos: pos + int(lens[i])].tobytes())
-        pos += int(lens[i])
-    assert pos == out_len.value
-    return out
+    return _compress_ranges(lib.nlzm_hip_compress_ranges_typed, src, ranges, (_elems(elems),), hist_bits, dedup)
 
 
 def decompress_typed(blob, block_lens, raw_lens, elems) -> list[bytes]:
@@ -345,12 +250,8 @@ def decompress_typed(blob, block_lens, raw_lens, elems) -> list[bytes]:
     lib = load_library()
     src = _bytes_in(blob)
     k = len(elems)
-    for name, v in (("block_lens", block_lens), ("raw_lens", raw_lens)):
-        if v is not None and len(v) != k:
-            raise ValueError(f"{name}: one entry per block")
-    blen = (C.c_uint64 * k)(*[int(x) for x in block_lens]) if block_lens is not None else None
-    raw = (C.c_uint64 * max(1, k))(*[int(x) for x in raw_lens]) if raw_lens is not None else None
-    el = (C.c_uint8 * max(1, k))(*[int(e) if 0 <= int(e) < 256 else 0 for e in elems])
+    _one_per_block(k, block_lens=block_lens, raw_lens=raw_lens)
+    blen, raw, el = _arr(C.c_uint64, block_lens), _arr(C.c_uint64, raw_lens, 1), _elems(elems, 1)
     got, total = (C.c_uint64 * max(1, k))(), C.c_uint64(0)
     if raw is None:
         _chk(lib.nlzm_hip_decompress_blocks_typed(src.ctypes.data, src.size, k, blen, None, el, None, 0, got, C.byref(total)))
@@ -358,12 +259,7 @@ def decompress_typed(blob, block_lens, raw_lens, elems) -> list[bytes]:
     cap = sum(int(raw[i]) for i in range(k))
     dst = np.empty(max(1, cap), dtype=np.uint8)
     _chk(lib.nlzm_hip_decompress_blocks_typed(src.ctypes.data, src.size, k, blen, raw, el, dst.ctypes.data, cap, got, C.byref(total)))
-    out, pos = [], 0
-    for i in range(k):
-        out.append(dst[pos: pos + int(got[i])].tobytes())
-        pos += int(got[i])
-    assert pos == total.value
-    return out
+    return _cut(dst, got[:k], total.value)
 
 
 def _tensor_elem(t) -> int:
@@ -388,8 +284,7 @@ def compress_tensors(tensors, hist_bits: int = 22, dedup: bool = False):
     for l in lens:
         at.append(n)
         n += l
-    off, ln = (C.c_uint64 * k)(*at), (C.c_uint64 * k)(*lens)
-    el = (C.c_uint8 * k)(*[_tensor_elem(t) for t in tensors])
+    off, ln, el = _arr(C.c_uint64, at), _arr(C.c_uint64, lens), _arr(C.c_uint8, [_tensor_elem(t) for t in tensors])
     cap = int(lib.nlzm_hip_compress_ranges_bound(k, ln))
     out = torch.empty(max(1, cap), dtype=torch.uint8, device=dev)
     blen, got = (C.c_uint64 * k)(), C.c_uint64(0)
@@ -406,8 +301,7 @@ def decompress_tensors(container, meta):
     k = len(meta)
     if not 1 <= k <= 65536:
         raise ValueError("meta: 1 to 65536 entries")
-    blen, raw = (C.c_uint64 * k)(*[int(m[0]) for m in meta]), (C.c_uint64 * k)(*[int(m[1]) for m in meta])
-    el = (C.c_uint8 * k)(*[int(m[2]) for m in meta])
+    blen, raw, el = _arr(C.c_uint64, [m[0] for m in meta]), _arr(C.c_uint64, [m[1] for m in meta]), _arr(C.c_uint8, [m[2] for m in meta])
     total = sum(int(m[1]) for m in meta)
     src = container.contiguous()
     dst = torch.empty(max(1, total), dtype=torch.uint8, device=src.device)
@@ -415,11 +309,8 @@ def decompress_tensors(container, meta):
     torch.cuda.synchronize()
     _chk(lib.nlzm_hip_decompress_blocks_typed_dev(src.data_ptr(), int(src.numel()), k, blen, raw, el, dst.data_ptr(), total, None, C.byref(got)))
     assert got.value == total
-    out, pos = [], 0
-    for _, r, _, dtype, shape in meta:
-        out.append(dst[pos: pos + r].clone().view(dtype).reshape(shape))
-        pos += r
-    return out
+    pieces = _cut(dst, [m[1] for m in meta], take=lambda piece: piece.clone())
+    return [p.view(m[3]).reshape(m[4]) for p, m in zip(pieces, meta)]
 
 
 def cut_points(data, avg_bits: int, min_len=None, max_len=None) -> list[int]:
@@ -433,7 +324,7 @@ def cut_points(data, avg_bits: int, min_len=None, max_len=None) -> list[int]:
     cap = min(n // max(lo, 1), 0xFFFFFFFF) if lo > 0 else 0
     cuts = (C.c_uint64 * max(1, cap))()
     got = C.c_uint32(0)
-    _chk(lib.nlzm_hip_cut_points(src.ctypes.data if n else None, n, avg_bits, lo, hi, cuts, cap, C.byref(got)))
+    _chk(lib.nlzm_hip_cut_points(_ptr(src), n, avg_bits, lo, hi, cuts, cap, C.byref(got)))
     return [int(cuts[i]) for i in range(got.value)]
 
 
@@ -449,7 +340,7 @@ def compress_fed(data, hist_bits: int = 22, piece: int = 1 << 20) -> bytes:
     """The streaming form of compress(): the input handed over `piece` bytes at a time (pinned staging, uploads overlapped
     with the launches), the stream taken back as its frames are finished (NLZM.cpp:1774-1778, :1853, :1870-1885)."""
     lib = load_library()
-    src = np.ascontiguousarray(np.frombuffer(data, dtype=np.uint8) if not isinstance(data, np.ndarray) else data)
+    src = _bytes_in(data)
     n = int(src.size)
     _chk(lib.nlzm_hip_feed_begin(n, hist_bits))
     buf = np.empty(1 << 20, dtype=np.uint8)
@@ -479,7 +370,7 @@ def compress_blocks_multi(data, devices: list[int], blocks_per_dev: int, hist_bi
     """len(devices) * blocks_per_dev independent streams, blocks_per_dev of them in flight on each listed GPU of this node
     (one host thread per GPU inside the library, no traffic between the GPUs but the final gather onto devices[0])."""
     lib = load_library()
-    src = np.ascontiguousarray(np.frombuffer(data, dtype=np.uint8) if not isinstance(data, np.ndarray) else data)
+    src = _bytes_in(data)
     n = int(src.size)
     nblocks = len(devices) * blocks_per_dev
     cap = int(lib.nlzm_hip_compress_bound(n)) + nblocks * (16 + 131072)
@@ -487,18 +378,9 @@ def compress_blocks_multi(data, devices: list[int], blocks_per_dev: int, hist_bi
     lens = (C.c_uint64 * nblocks)()
     out_len = C.c_uint64(0)
     devs = (C.c_int * len(devices))(*devices)
-    _chk(lib.nlzm_hip_compress_blocks_multi(devs, len(devices), blocks_per_dev, src.ctypes.data if n else None, n, hist_bits,
+    _chk(lib.nlzm_hip_compress_blocks_multi(devs, len(devices), blocks_per_dev, _ptr(src), n, hist_bits,
                                             dst.ctypes.data, cap, lens, C.byref(out_len)))
-    out, pos = [], 0
-    for i in range(nblocks):
-        out.append(dst[pos: pos + int(lens[i])].tobytes())
-        pos += int(lens[i])
-    assert pos == out_len.value
-    return out
-
-
-def _bytes_in(data) -> np.ndarray:
-    return np.ascontiguousarray(np.frombuffer(data, dtype=np.uint8) if not isinstance(data, np.ndarray) else data)
+    return _cut(dst, lens, out_len.value)
 
 
 def decompress(stream) -> bytes:
@@ -515,11 +397,7 @@ def decompress_blocks(blob, nblocks: int) -> list[bytes]:
     _chk(lib.nlzm_hip_decompress_blocks(src.ctypes.data, src.size, nblocks, None, None, None, 0, raw, C.byref(total)))
     dst = np.empty(max(1, total.value), dtype=np.uint8)
     _chk(lib.nlzm_hip_decompress_blocks(src.ctypes.data, src.size, nblocks, None, raw, dst.ctypes.data, total.value, raw, C.byref(total)))
-    out, pos = [], 0
-    for i in range(nblocks):
-        out.append(dst[pos: pos + int(raw[i])].tobytes())
-        pos += int(raw[i])
-    return out
+    return _cut(dst, raw)
 
 
 class LengthMismatch(NlzmError):
@@ -547,7 +425,7 @@ def verify(blob, data, nblocks: int = 1) -> int:
     lib = load_library()
     src, orig = _bytes_in(blob), _bytes_in(data)
     first, decoded = C.c_uint64(0), C.c_uint64(0)
-    _chk(lib.nlzm_hip_verify(src.ctypes.data, src.size, nblocks, None, orig.ctypes.data if orig.size else None, orig.size, C.byref(first), C.byref(decoded)))
+    _chk(lib.nlzm_hip_verify(src.ctypes.data, src.size, nblocks, None, _ptr(orig), orig.size, C.byref(first), C.byref(decoded)))
     return verify_verdict(int(first.value), int(decoded.value), int(orig.size))
 
 
@@ -556,7 +434,7 @@ def crc32(data, seed: int = 0) -> int:
     lib = load_library()
     src = _bytes_in(data)
     out = C.c_uint32(0)
-    _chk(lib.nlzm_hip_crc32(src.ctypes.data if src.size else None, src.size, seed & 0xFFFFFFFF, C.byref(out)))
+    _chk(lib.nlzm_hip_crc32(_ptr(src), src.size, seed & 0xFFFFFFFF, C.byref(out)))
     return int(out.value)
 
 
@@ -564,9 +442,9 @@ def crc32_ranges(data, ranges) -> list[int]:
     """The CRC32 of every (offset, length) range of `data`, all in one call on the device; the ranges may be empty and may overlap."""
     lib = load_library()
     src = _bytes_in(data)
-    k = len(ranges)
-    off, ln, out = (C.c_uint64 * max(1, k))(*[int(o) for o, _ in ranges]), (C.c_uint64 * max(1, k))(*[int(l) for _, l in ranges]), (C.c_uint32 * max(1, k))()
-    _chk(lib.nlzm_hip_crc32_ranges(src.ctypes.data if src.size else None, src.size, k, off, ln, out))
+    k, off, ln = _ranges(ranges, 1)
+    out = (C.c_uint32 * max(1, k))()
+    _chk(lib.nlzm_hip_crc32_ranges(_ptr(src), src.size, k, off, ln, out))
     return [int(out[i]) for i in range(k)]
 
 
@@ -582,10 +460,8 @@ def check(blob, crcs, nblocks: int = 1, raw_lens=None) -> int:
     src = _bytes_in(blob)
     if len(crcs) != nblocks or (raw_lens is not None and len(raw_lens) != nblocks):
         raise ValueError("one CRC (and one length) per block")
-    want = (C.c_uint32 * nblocks)(*[int(c) & 0xFFFFFFFF for c in crcs])
-    raw = (C.c_uint64 * nblocks)(*[int(r) for r in raw_lens]) if raw_lens is not None else None
     bad = C.c_uint32(0)
-    _chk(lib.nlzm_hip_check(src.ctypes.data, src.size, nblocks, None, raw, want, C.byref(bad), None))
+    _chk(lib.nlzm_hip_check(src.ctypes.data, src.size, nblocks, None, _arr(C.c_uint64, raw_lens), _crcs(crcs), C.byref(bad), None))
     return int(bad.value)
 
 
@@ -604,26 +480,16 @@ def read_ranges(blob, ranges, nblocks: int = 1, block_lens=None, raw_lens=None, 
     that differs (blocks read in part cannot be checked)."""
     lib = load_library()
     src = _bytes_in(blob)
-    k = len(ranges)
-    for name, v in (("block_lens", block_lens), ("raw_lens", raw_lens), ("crcs", crcs)):
-        if v is not None and len(v) != nblocks:
-            raise ValueError(f"{name}: one entry per block")
-    off, ln = (C.c_uint64 * max(1, k))(*[int(o) for o, _ in ranges]), (C.c_uint64 * max(1, k))(*[int(l) for _, l in ranges])
-    blen = (C.c_uint64 * nblocks)(*[int(x) for x in block_lens]) if block_lens is not None else None
-    raw = (C.c_uint64 * nblocks)(*[int(x) for x in raw_lens]) if raw_lens is not None else None
-    want = (C.c_uint32 * nblocks)(*[int(c) & 0xFFFFFFFF for c in crcs]) if crcs is not None else None
+    _one_per_block(nblocks, block_lens=block_lens, raw_lens=raw_lens, crcs=crcs)
+    k, off, ln = _ranges(ranges, 1)
     cap = sum(int(l) for _, l in ranges)
     dst = np.empty(max(1, cap), dtype=np.uint8)
     got, bad = C.c_uint64(0), C.c_uint32(nblocks)
-    _chk(lib.nlzm_hip_read_ranges(src.ctypes.data, src.size, nblocks, blen, raw, want, k, off, ln, dst.ctypes.data, cap, C.byref(got), C.byref(bad)))
+    _chk(lib.nlzm_hip_read_ranges(src.ctypes.data, src.size, nblocks, _arr(C.c_uint64, block_lens), _arr(C.c_uint64, raw_lens), _crcs(crcs), k, off, ln,
+                                  dst.ctypes.data, cap, C.byref(got), C.byref(bad)))
     if bad.value < nblocks:
         raise CrcMismatch(int(bad.value))
-    out, pos = [], 0
-    for _, l in ranges:
-        out.append(dst[pos: pos + int(l)].tobytes())
-        pos += int(l)
-    assert pos == got.value
-    return out
+    return _cut(dst, [l for _, l in ranges], got.value)
 
 
 def read_range(blob, off: int, length: int, nblocks: int = 1, block_lens=None, raw_lens=None, crcs=None) -> bytes:
@@ -640,11 +506,8 @@ class Decoder:
     def __init__(self, blob, nblocks: int = 1, block_lens=None, raw_lens=None):
         lib = load_library()
         src = _bytes_in(blob)
-        for name, v in (("block_lens", block_lens), ("raw_lens", raw_lens)):
-            if v is not None and len(v) != nblocks:
-                raise ValueError(f"{name}: one entry per block")
-        blen = (C.c_uint64 * nblocks)(*[int(x) for x in block_lens]) if block_lens is not None else None
-        raw = (C.c_uint64 * nblocks)(*[int(x) for x in raw_lens]) if raw_lens is not None else None
+        _one_per_block(nblocks, block_lens=block_lens, raw_lens=raw_lens)
+        blen, raw = _arr(C.c_uint64, block_lens), _arr(C.c_uint64, raw_lens)
         if raw is None:          # (the lengths are wanted here too: read() addresses the decoded bytes)
             raw, total = (C.c_uint64 * nblocks)(), C.c_uint64(0)
             _chk(lib.nlzm_hip_decompress_blocks(src.ctypes.data, src.size, nblocks, blen, None, None, 0, raw, C.byref(total)))
@@ -664,7 +527,7 @@ class Decoder:
             raise NlzmError("the decoder is closed")
         if targets is not None and len(targets) != self.nblocks:
             raise ValueError("targets: one entry per block")
-        tg = (C.c_uint64 * self.nblocks)(*[min(int(t), TO_THE_END) for t in targets]) if targets is not None else None
+        tg = None if targets is None else _arr(C.c_uint64, [min(int(t), TO_THE_END) for t in targets])
         done, fin, ms = (C.c_uint64 * self.nblocks)(), C.c_int(0), C.c_double(0)
         rc = load_library().nlzm_hip_decode_step(max_frames, tg, done, C.byref(fin), C.byref(ms))
         if rc:
@@ -702,66 +565,6 @@ class Decoder:
     def __exit__(self, *exc):
         self.close()
         return False
-
-
-def read_index_typed(path):
-    """The sidecar index of a block container in every version: (block_lens, raw_lens, crcs or None, elems).  `nlzm c -blocks:k` writes NLZMIDX 1
-    (`off len raw` per block), with -crc NLZMIDX 2 (a CRC32 behind them, and the whole file's behind the header's fields), with -elem:E NLZMIDX 3
-    (the block's element size behind that; the CRC32s are the RAW bytes').  Versions 1 and 2 have every element size 1.  The structural checks are
-    the command line's: offsets back to back, no sum that wraps 64 bits, block lengths summing to the header's n_out and raw lengths to its n_in; an
-    element size outside 1, 2, 4, 8 is refused.  ValueError when the file is not such an index."""
-    words = open(path, "r").read().split()
-    M = 1 << 64
-
-    def num(w, base=10):
-        try:
-            v = int(w, base)
-        except ValueError:
-            raise ValueError(f"{path}: {w!r} is not a number") from None
-        if not 0 <= v < M:
-            raise ValueError(f"{path}: {w} does not fit 64 bits")
-        return v
-
-    if len(words) < 2 or words[0] != "NLZMIDX" or words[1] not in ("1", "2", "3"):
-        raise ValueError(f"{path}: not an NLZMIDX 1 or 2 file")
-    ver = int(words[1])
-    head, per = 5 + (ver >= 2), 2 + ver                  # (the header's fields, an entry's)
-    if len(words) < (6 if ver == 3 else 5):
-        raise ValueError(f"{path}: not an NLZMIDX 3 file" if ver == 3 else f"{path}: not an NLZMIDX 1 or 2 file")
-    k, n_in, n_out = num(words[2]), num(words[3]), num(words[4])
-    if not 1 <= k <= 65536 or len(words) != head + per * k:
-        raise ValueError(f"{path}: {k} blocks do not fit the file's {len(words)} fields")
-    if ver >= 2 and num(words[5], 16) >= 1 << 32:
-        raise ValueError(f"{path}: the whole file's CRC32 does not fit 32 bits")
-    lens, raws, crcs, elems, expect, raw_sum = [], [], [], [], 0, 0
-    for i in range(k):
-        f = words[head + per * i: head + per * (i + 1)]
-        off, ln, raw = num(f[0]), num(f[1]), num(f[2])
-        c, e = (num(f[3], 16), num(f[4])) if ver == 3 else (0, 1)
-        if off != expect or ln < 8 or off + ln >= M or ln > n_out - expect or raw > n_in - raw_sum:
-            raise ValueError(f"{path}: block {i + 1}'s entry does not fit (offset {off}, length {ln}, raw length {raw})")
-        if ver == 2:                                     # (read behind the entry's check, as version 2 always was)
-            c = num(f[3], 16)
-        if c >= 1 << 32:
-            raise ValueError(f"{path}: block {i + 1}'s CRC32 does not fit 32 bits")
-        if e not in (1, 2, 4, 8):
-            raise ValueError(f"{path}: block {i + 1}'s element size {e} is not 1, 2, 4 or 8")
-        lens.append(ln)
-        raws.append(raw)
-        crcs.append(c)
-        elems.append(e)
-        expect, raw_sum = expect + ln, raw_sum + raw
-    if expect != n_out or raw_sum != n_in:
-        raise ValueError(f"{path}: the blocks' lengths sum to {expect} / {raw_sum}, the header says {n_out} / {n_in}")
-    return lens, raws, (crcs if ver >= 2 else None), elems
-
-
-def read_index(path):
-    """read_index_typed for the versions without typed blocks (NLZMIDX 1 and 2): (block_lens, raw_lens, crcs or None).  Version 3 is refused."""
-    words = open(path, "r").read().split()
-    if len(words) < 5 or words[0] != "NLZMIDX" or words[1] not in ("1", "2"):
-        raise ValueError(f"{path}: not an NLZMIDX 1 or 2 file")
-    return read_index_typed(path)[:3]
 
 
 def stats() -> dict:
@@ -805,7 +608,7 @@ def rans_frames(frames: list[tuple[np.ndarray, np.ndarray, int]]) -> list[bytes]
 
 def find_matches(data, hist_bits: int, pos_lo: int, pos_hi: int, cap_words: int = 1 << 24) -> np.ndarray:
     lib = load_library()
-    src = np.ascontiguousarray(np.frombuffer(data, dtype=np.uint8) if not isinstance(data, np.ndarray) else data)
+    src = _bytes_in(data)
     out = np.empty(cap_words, dtype=np.uint32)
     used = C.c_uint64(0)
     _chk(lib.nlzm_hip_find_matches(src.ctypes.data, src.size, hist_bits, pos_lo, pos_hi, out.ctypes.data, cap_words,
@@ -815,7 +618,7 @@ def find_matches(data, hist_bits: int, pos_lo: int, pos_hi: int, cap_words: int 
 
 def parse_emit(data, hist_bits: int, frame_idx: int):
     lib = load_library()
-    src = np.ascontiguousarray(np.frombuffer(data, dtype=np.uint8) if not isinstance(data, np.ndarray) else data)
+    src = _bytes_in(data)
     syms = np.empty(1 << 19, dtype=np.uint32)
     bits = np.empty(1 << 18, dtype=np.uint8)
     sizes = np.zeros(3, dtype=np.uint32)

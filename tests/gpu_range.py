@@ -66,14 +66,7 @@ import torch
 if other_lib:
     if parts != ["full"]:
         raise SystemExit("--lib: only the part `full`")
-    lib = C.CDLL(other_lib)
-    u64p = C.POINTER(C.c_uint64)
-    lib.nlzm_hip_init.argtypes = [C.c_int]
-    lib.nlzm_hip_last_error.restype = C.c_char_p
-    lib.nlzm_hip_compress_bound.argtypes, lib.nlzm_hip_compress_bound.restype = [C.c_uint64], C.c_uint64
-    lib.nlzm_hip_compress_dev.argtypes = [C.c_void_p, C.c_uint64, C.c_uint32, C.c_void_p, C.c_uint64, u64p]
-    lib.nlzm_hip_decompress_dev.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, u64p]
-    lib.nlzm_hip_get_counter.argtypes = [C.c_char_p, u64p]
+    lib = nlzm_amd._abi.bind(C.CDLL(other_lib))
 else:
     lib = nlzm_amd.load_library()
 if lib.nlzm_hip_init(0):

@@ -1,12 +1,15 @@
 """CPU suite: the C-ABI library loads and exports exactly what include/nlzm_hip.h declares;
 without a GPU every compute entry fails loudly (there is no CPU fallback)."""
+import ctypes as C
 import os
 import re
 import subprocess
+from types import SimpleNamespace
 
 import pytest
 
 import nlzm_amd
+from nlzm_amd import _abi
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -28,6 +31,69 @@ def test_header_symbols_exported(lib):
     assert syms == sorted(nlzm_amd.ABI_SYMBOLS)
     for s in syms:
         assert hasattr(lib, s), f"{s} declared in include/nlzm_hip.h but not exported"
+
+
+def declared_prototypes():
+    """{name: (return type, [parameter, ...])} of every function the header declares, as C text with the comments gone"""
+    txt = open(os.path.join(ROOT, "include", "nlzm_hip.h")).read()
+    txt = re.sub(r"/\*.*?\*/", "", txt, flags=re.S)
+    txt = re.sub(r"^[ \t]*#.*$", "", txt, flags=re.M)          # (a #define stands directly in front of a prototype)
+    found = re.findall(r"([\w\s*]+?)\b(nlzm_hip_\w+)\s*\(([^)]*)\)\s*;", txt)
+    return {name: (ret, [a for a in args.split(",") if a.split() != ["void"]]) for ret, name, args in found}
+
+
+C_SCALARS = {"void": None, "int": C.c_int, "int64_t": C.c_int64, "uint8_t": C.c_uint8, "uint32_t": C.c_uint32, "uint64_t": C.c_uint64,
+             "double": C.c_double, "nlzm_hip_stats": nlzm_amd.Stats, "nlzm_hip_timing": nlzm_amd.Timing}
+# The three stage entry points are handed numpy addresses (integers) for their typed arrays too, so the table has c_void_p where the header
+# has a uint32_t * or uint64_t *: these positions, and no other, are held to "a pointer" alone.
+ADDRESS_ONLY = {"nlzm_hip_rans_frames": {0, 1, 3, 4, 8}, "nlzm_hip_find_matches": {5}, "nlzm_hip_parse_emit": {4, 8}}
+
+
+def ctypes_for(text):
+    """what the table may have for a C return or parameter type: the parameter's name, if any, is dropped"""
+    words = [w for w in text.replace("*", " * ").split() if w != "const"]
+    base, stars = words[0], words.count("*")
+    assert stars <= 1, text
+    if not stars:
+        return [C_SCALARS[base]]
+    if base == "char":
+        return [C.c_char_p]
+    if base in ("void", "uint8_t"):
+        return [C.c_void_p, C.POINTER(C.c_uint8)]
+    return [C.POINTER(C_SCALARS[base])]
+
+
+def test_signature_table_matches_the_header():
+    """every row of nlzm_amd/_abi.py against its prototype in include/nlzm_hip.h: the return type, the number of parameters, every integer's
+    width and signedness, double, const char * as c_char_p, a pointer wherever the header has one and to what it points to (void * and
+    uint8_t * as c_void_p or POINTER(c_uint8))"""
+    protos = declared_prototypes()
+    assert sorted(protos) == declared_symbols() == sorted(_abi.TABLE) and len(protos) == 67
+    bad = []
+    for name, (ret, params) in protos.items():
+        restype, argtypes = _abi.TABLE[name]
+        if restype not in ctypes_for(ret):
+            bad.append((name, "returns", " ".join(ret.split()), restype))
+        if len(argtypes) != len(params):
+            bad.append((name, "takes", len(params), len(argtypes)))
+            continue
+        for i, (param, have) in enumerate(zip(params, argtypes)):
+            if i in ADDRESS_ONLY.get(name, ()):
+                ok = "*" in param and have is C.c_void_p and C.c_void_p not in ctypes_for(param)
+            else:
+                ok = have in ctypes_for(param)
+            if not ok:
+                bad.append((name, i, " ".join(param.split()), have))
+    assert not bad, bad
+
+
+def test_bind_skips_what_a_library_lacks():
+    """a build of an earlier commit (NLZM_LIB) exports fewer symbols: those it has get their rows, the others are passed over"""
+    old = SimpleNamespace(nlzm_hip_init=SimpleNamespace(), nlzm_hip_compress_bound=SimpleNamespace())
+    assert _abi.bind(old) is old
+    assert old.nlzm_hip_init.argtypes == [C.c_int] and old.nlzm_hip_init.restype is C.c_int
+    assert old.nlzm_hip_compress_bound.argtypes == [C.c_uint64] and old.nlzm_hip_compress_bound.restype is C.c_uint64
+    assert sorted(vars(old)) == ["nlzm_hip_compress_bound", "nlzm_hip_init"]
 
 
 def test_only_c_abi_is_exported():
@@ -63,10 +129,7 @@ def test_block_mode_placement_rule(lib):
     """The persistent launch of a block set deals every stream's workgroups (three stages + its worker CUs) to ONE XCD when the
     number of streams is a multiple of eight (workgroups go to the XCDs round-robin: equal index modulo 8), and in every case
     each (stream, block) pair is some workgroup exactly once.  No device needed."""
-    import ctypes as C
     f = lib.nlzm_hip_block_placement
-    f.restype = None
-    f.argtypes = [C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
     for nstreams in (1, 3, 8, 16, 24, 32, 40, 64):
         for bps in (4, 5, 7, 8, 31):
             seen = {}
