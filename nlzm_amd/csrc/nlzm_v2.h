@@ -17,6 +17,8 @@
 // that tests/host_sim/sim2.cpp checks against the oracle.  All file:line cites are NLZM.cpp.
 #pragma once
 
+#include <stddef.h>
+
 #include "nlzm_core.h"
 #include "xw.h"
 
@@ -1878,26 +1880,30 @@ struct Parser {
                           uint32_t &o2, uint32_t &o3, uint32_t &link, uint32_t &delta) const
     {
         const uint32_t src = (uint32_t)(key >> 8) & 0xFFFFFFu, rank = (uint32_t)key & 0xFFu;
-        if (src == kSrcNone) { o0 = rep0; o1 = rep1; o2 = rep2; o3 = rep3; link = kSrcNone; delta = 0; return; }   // node 0 (:1476)
-        const uint32_t *sr = src >= b0 ? L()->brep[pbuf] + (src - b0) * 4 : L()->nrep + (src & 511u) * 4;
+        // No ladder of conditions around the loads: the source's set and the edge's distance are asked for together, in every lane, at
+        // addresses that are good for any key (node 0 has no source, and a key that is none names no node: both read node 0's words and
+        // drop them), and the rest is a choice between values.  A condition around each load is an LDS round trip of its own in the
+        // update's chain.
+        const bool none = src == kSrcNone;                          // node 0 (:1476)
+        const uint32_t s = src < kSrcNone ? src : 0u;
+        const bool lit = rank == kRankLit, sampled = rank < kRankProbe, probe = !sampled && !lit;
+        // (of a finished block from the ring, of this block from brep, which lies behind the ring: one base, the word chosen)
+        static_assert(offsetof(PLds, brep) == offsetof(PLds, nrep) + sizeof(uint32_t) * 512 * 4, "brep follows nrep");
+        const uint32_t in_ring = (s & 511u) * 4, in_block = 512u * 4 + pbuf * 64u * 4 + (s - b0) * 4;
+        const uint32_t *sr = (const uint32_t *)((const char *)L() + offsetof(PLds, nrep)) + (s >= b0 ? in_block : in_ring);
         const uint32_t s0 = sr[0], s1 = sr[1], s2 = sr[2], s3 = sr[3];
-        o0 = s0; o1 = s1; o2 = s2; o3 = s3;
-        uint32_t cmd = 0, len = 0, idx = 0;
-        delta = 0;
-        if (rank != kRankLit) {
-            len = node - src;
-            if (rank >= kRankProbe) { cmd = 2; idx = rank - kRankProbe; delta = idx == 0 ? s0 : (idx == 1 ? s1 : (idx == 2 ? s2 : s3)); }
-            else {
-                const uint32_t d = L()->edge_d[((seg_a + src) & 511u) * kMaxEdges + (rank >> 1)];
-                delta = d;
-                if (rank & 1u) { cmd = 2; idx = d == s0 ? 0u : (d == s1 ? 1u : (d == s2 ? 2u : 3u)); }
-                else {
-                    cmd = 1;
-                    if (!(d == s0 || d == s1 || d == s2 || d == s3)) { o0 = d; o1 = s0; o2 = s1; o3 = s2; }
-                }
-            }
-        }
-        link = src | (len << 13) | (cmd << 22) | (idx << 24);
+        const uint32_t d = L()->edge_d[((seg_a + s) & 511u) * kMaxEdges + (sampled ? rank >> 1 : 0u)];
+        const bool as_rep = sampled && (rank & 1u), as_dict = sampled && !(rank & 1u);
+        const uint32_t pidx = rank - kRankProbe;                    // (a probe's: the rep slot it measured)
+        const uint32_t idx = probe ? pidx : (as_rep ? (d == s0 ? 0u : (d == s1 ? 1u : (d == s2 ? 2u : 3u))) : 0u);
+        const uint32_t cmd = lit ? 0u : (as_dict ? 1u : 2u);
+        const uint32_t len = lit ? 0u : node - src;
+        const uint32_t pd = pidx == 0 ? s0 : (pidx == 1 ? s1 : (pidx == 2 ? s2 : s3));
+        const bool shift = as_dict & (umin(umin(d ^ s0, d ^ s1), umin(d ^ s2, d ^ s3)) != 0);     // a dict edge's distance that is not in the set goes in front
+        o0 = none ? rep0 : (shift ? d : s0); o1 = none ? rep1 : (shift ? s0 : s1);
+        o2 = none ? rep2 : (shift ? s1 : s2); o3 = none ? rep3 : (shift ? s2 : s3);
+        delta = (none || lit) ? 0u : (sampled ? d : pd);
+        link = none ? kSrcNone : (src | (len << 13) | (cmd << 22) | (idx << 24));
     }
 
     // the loader wave: how many nodes the block at node b0 gets (sh[0]), and this stage's progress word
@@ -2355,12 +2361,21 @@ struct Parser {
                 const unsigned long long k1 = ptick();
                 if (pass > 0) xw::block_sync();
                 const unsigned long long k2 = ptick();
+                // pass-update: begin
                 // ---- update: every node of the block from the keys (the same in every wave)
-                unsigned long long kin = kKeyNone;
-                if (inb) {
-                    if (node <= end_open) kin = L()->mprev[node & 511u];
-                    if (i >= 1 && pass > 0) { const unsigned long long kc = L()->mcur[buf][node & 511u]; if (kc < kin) kin = kc; }
-                }
+                // The update is one chain on every wave's critical path, so it is written for its length: three
+                // dependent LDS round trips -- the keys with the reach word, the winners' sets with the edge's distance, the shuffles of
+                // the literal runs -- and choices between values instead of branches, which leaves the three scans in one basic block
+                // where the compiler fills the wait states of one scan's DPP steps with another's.  ~170 instructions where there were
+                // ~200 with four round trips; 1,180 cycles a pass on the parser stage's probe waves where there were 1,580 (profile
+                // build, 100 MB of text).  tests/isa_pass.py counts it between the two markers, tests/test_isa_pass.py holds it.
+                // (Everything the update reads from LDS in front of the winners' sets is asked for here, in one go and in every lane: the
+                //  two keys and the reach word are independent of each other and of the scans, and a condition around a load puts its
+                //  round trip behind whatever decides the condition.  What a lane has no use for, it drops.)
+                const unsigned long long kp_w = L()->mprev[node & 511u], kc_w = L()->mcur[buf][node & 511u];
+                const uint32_t reach_w = L()->reach[buf][i];
+                unsigned long long kin = (inb & (node <= end_open)) ? kp_w : kKeyNone;
+                if (inb && i >= 1 && pass > 0 && kc_w < kin) kin = kc_w;
                 const uint32_t mc = kin == kKeyNone ? kInf : (uint32_t)(kin >> 32);
                 // cost through the literal edges: c[i] = min(mc[i], c[i-1] + litw[i-1]) = S[i] + min_{j<=i} (mc[j] - S[j])
                 const uint32_t nc = (uint32_t)(xw::scan_min_i32((int32_t)mc - (int32_t)S) + (int32_t)S);
@@ -2371,7 +2386,7 @@ struct Parser {
                 // (pass 0: the reach of the SAMPLED edges does not depend on the prices -- max_len is the table's (:1550) -- and the
                 //  first node that no node before it reaches is where the unconditional prefix maximum stops covering, so the
                 //  block's membership is known before anything is relaxed; only a probe's reach (:1608-1612) is found on the way)
-                const uint32_t rlive = pass == 0 ? sreach : (lv ? L()->reach[buf][i] : 0u);     // (a node's reach counts once it was inside: it has relaxed its edges)
+                const uint32_t rlive = pass == 0 ? sreach : (lv ? reach_w : 0u);       // (a node's reach counts once it was inside: it has relaxed its edges)
                 const uint32_t pm = xw::scan_max(rlive);
                 const uint32_t before = umax(xw::lane_below(pm, 0u), end_p);
                 const bool inside = inb && node < before;
@@ -2381,17 +2396,23 @@ struct Parser {
                 const bool nlv = i < istar && inb;
                 const unsigned long long u2 = ptick();
                 // rep sets from the winners (the sources' sets as of the last pass)
-                uint32_t o0 = 0, o1 = 0, o2 = 0, o3 = 0, link = 0, delta = 0;
-                if (act && nkey != kKeyNone) winner_set(seg_a, b0, (pass + 1) & 1u, node, nkey, o0, o1, o2, o3, link, delta);
+                // (the lane a literal run takes its set from depends on the costs alone: found while the winners' sets are on their way)
+                const uint32_t root = xw::scan_max(litwin ? 0u : i);
+                uint32_t o0, o1, o2, o3, link, delta;
+                winner_set(seg_a, b0, (pass + 1) & 1u, node, nkey, o0, o1, o2, o3, link, delta);      // (every lane: no branch around its loads)
+                const bool won = act & (nkey != kKeyNone);
+                o0 = won ? o0 : 0u; o1 = won ? o1 : 0u; o2 = won ? o2 : 0u; o3 = won ? o3 : 0u;
                 {   // a run of literal winners carries the set of the node in front of the run (:1498): taken from that lane
                     // in THIS pass, so that a literal run costs no pass
-                    const uint32_t root = xw::scan_max(litwin ? 0u : i);
                     const uint32_t t0 = xw::shfl(o0, root), t1 = xw::shfl(o1, root), t2 = xw::shfl(o2, root), t3 = xw::shfl(o3, root);
-                    if (litwin) { o0 = t0; o1 = t1; o2 = t2; o3 = t3; }
+                    o0 = litwin ? t0 : o0; o1 = litwin ? t1 : o1; o2 = litwin ? t2 : o2; o3 = litwin ? t3 : o3;
                 }
                 const unsigned long long u3 = ptick();
-                const bool same = !act || (key == nkey && r0 == o0 && r1 == o1 && r2 == o2 && r3 == o3 && lv == nlv);
+                const uint32_t diff = (uint32_t)(key ^ nkey) | (uint32_t)((key ^ nkey) >> 32) | (r0 ^ o0) | (r1 ^ o1) | (r2 ^ o2) | (r3 ^ o3);
+                const bool same = (!act) | ((diff == 0) & (lv == nlv));
                 const bool changed = xw::any(!same);
+                // (the one choice left as a branch: written as seven selects it is two instructions shorter, and the kernels' scalar
+                //  registers then spill beyond tests/golden/isa_spill_budget.json in stages this change does not touch)
                 if (act) { key = nkey; c = nc; r0 = o0; r1 = o1; r2 = o2; r3 = o3; }
                 lv = nlv;
                 if (w == 0 && act) { uint32_t *dr = L()->brep[pass & 1u] + i * 4; dr[0] = o0; dr[1] = o1; dr[2] = o2; dr[3] = o3; }
@@ -2399,6 +2420,7 @@ struct Parser {
                     const uint32_t done_n = umin(istar, nb);
                     blk_end = done_n ? umax(end_p, xw::readlane(pm, done_n - 1)) : end_p;
                 }
+                // pass-update: end
                 t_work += k1 - k0; t_bar += k2 - k1; t_upd += ptick() - k2;
                 t_s[0] += k0a - k0; t_s[1] += k0b - k0a; t_s[2] += k1 - k0b; t_s[3] += u1 - k2; t_s[4] += u2 - u1; t_s[5] += u3 - u2; t_s[6] += ptick() - u3;
                 if (!changed) break;
