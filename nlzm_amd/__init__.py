@@ -262,15 +262,63 @@ def decompress_typed(blob, block_lens, raw_lens, elems) -> list[bytes]:
     return _cut(dst, got[:k], total.value)
 
 
+def plane_costs(data, ranges, hist: bool = False):
+    """(C_1, C_2, C_4, C_8) of every (offset, length) range of `data`, counted on the device in one launch (nlzm_hip_plane_costs; the rule:
+    tests/elem_model.py): what the range's byte planes at element size 1, 2, 4 and 8 would cost an order-0 coder, in 2^-16 bits, model included.
+    hist: also the counts they were made from, an array of shape (k, 8, 256) -- H[c][v] of every range."""
+    lib = load_library()
+    src = _bytes_in(data)
+    if not 1 <= len(ranges) <= 65536:
+        raise ValueError("ranges: 1 to 65536")
+    k, off, ln = _ranges(ranges)
+    cost = (C.c_uint64 * (4 * k))()
+    h = np.zeros((k, 8, 256), dtype=np.uint64) if hist else None
+    _chk(lib.nlzm_hip_plane_costs(_ptr(src), int(src.size), k, off, ln, cost, None if h is None else h.ctypes.data_as(C.POINTER(C.c_uint64))))
+    costs = [tuple(int(cost[4 * i + j]) for j in range(4)) for i in range(k)]
+    return (costs, h) if hist else costs
+
+
+def choose_elem(costs, length: int) -> int:
+    """The element size (1, 2, 4 or 8) for a range of `length` bytes with the costs (C_1, C_2, C_4, C_8) (nlzm_hip_choose_elem); needs no device."""
+    if len(costs) != 4:
+        raise ValueError("costs: C_1, C_2, C_4, C_8")
+    return int(load_library().nlzm_hip_choose_elem(_arr(C.c_uint64, costs), int(length)))
+
+
+def choose_elems(data, ranges) -> list[int]:
+    """The element size chosen for every (offset, length) range of `data`: plane_costs and choose_elem in one call (nlzm_hip_choose_elems)."""
+    lib = load_library()
+    src = _bytes_in(data)
+    if not 1 <= len(ranges) <= 65536:
+        raise ValueError("ranges: 1 to 65536")
+    k, off, ln = _ranges(ranges)
+    el = (C.c_uint8 * k)()
+    _chk(lib.nlzm_hip_choose_elems(_ptr(src), int(src.size), k, off, ln, el))
+    return [int(e) for e in el]
+
+
+def compress_auto(data, ranges, hist_bits: int = 22, dedup: bool = False):
+    """compress_typed with the element sizes chosen on the device from the ranges' bytes (nlzm_hip_compress_ranges_auto): (streams, elems), and
+    decompress_typed reads the streams with elems."""
+    lib = load_library()
+    src = _bytes_in(data)
+    if not 1 <= len(ranges) <= 65536:
+        raise ValueError("ranges: 1 to 65536")
+    el = (C.c_uint8 * len(ranges))()
+    streams = _compress_ranges(lib.nlzm_hip_compress_ranges_auto, src, ranges, (el,), hist_bits, dedup)
+    return streams, [int(e) for e in el]
+
+
 def _tensor_elem(t) -> int:
     return t.element_size() if t.element_size() in (2, 4, 8) else 1
 
 
-def compress_tensors(tensors, hist_bits: int = 22, dedup: bool = False):
+def compress_tensors(tensors, hist_bits: int = 22, dedup: bool = False, auto: bool = False):
     """A list of torch tensors (any device, any dtype) as one block container in device memory, one block per tensor, filtered at the tensor's element
     size (1 when it is not 2, 4 or 8): the tensors are viewed as bytes and concatenated on the GPU, with the padding the compress path reads behind
-    them, and nlzm_hip_compress_ranges_typed_dev runs on data_ptr().  Returns (container, meta): a device uint8 tensor and a list of
-    (block_len, raw_len, elem, dtype, shape) per tensor -- what decompress_tensors takes."""
+    them, and nlzm_hip_compress_ranges_typed_dev runs on data_ptr().  auto: a tensor whose element size is 1 -- a uint8 tensor of packed records --
+    is filtered at the size chosen from its bytes (nlzm_hip_choose_elems_dev); every other tensor keeps its dtype's.  Returns (container, meta): a
+    device uint8 tensor and a list of (block_len, raw_len, elem, dtype, shape) per tensor -- what decompress_tensors takes."""
     import torch
     lib = load_library()
     k = len(tensors)
@@ -289,6 +337,12 @@ def compress_tensors(tensors, hist_bits: int = 22, dedup: bool = False):
     out = torch.empty(max(1, cap), dtype=torch.uint8, device=dev)
     blen, got = (C.c_uint64 * k)(), C.c_uint64(0)
     torch.cuda.synchronize()
+    bytewise = [i for i in range(k) if tensors[i].element_size() == 1] if auto else []
+    if bytewise:
+        chosen = (C.c_uint8 * len(bytewise))()
+        _chk(lib.nlzm_hip_choose_elems_dev(data.data_ptr(), n, len(bytewise), _arr(C.c_uint64, [at[i] for i in bytewise]), _arr(C.c_uint64, [lens[i] for i in bytewise]), chosen))
+        for i, e in zip(bytewise, chosen):
+            el[i] = e
     _with_dedup(dedup, lambda: _chk(lib.nlzm_hip_compress_ranges_typed_dev(data.data_ptr(), n, k, off, ln, el, hist_bits, out.data_ptr(), cap, blen, C.byref(got))))
     meta = [(int(blen[i]), lens[i], int(el[i]), tensors[i].dtype, tuple(tensors[i].shape)) for i in range(k)]
     return out[: got.value].clone(), meta

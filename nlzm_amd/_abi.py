@@ -2,6 +2,7 @@
 
 A host-buffer entry and its `_dev` twin take the same list and are declared together.  tests/test_abi.py parses the header's prototypes and
 holds every row to them (widths, signedness, pointer positions, pointee types), so a new entry point is one prototype there and one row here.
+ELEM_TABLE is the same for include/nlzm_hip_elem.h (the element sizes of typed ranges chosen on the device), held by tests/test_elem_abi.py.
 bind() gives a loaded library the rows of the symbols it exports: a build of an earlier commit, loaded through NLZM_LIB for an A/B run, lacks
 the newer ones and loads all the same.
 """
@@ -96,10 +97,26 @@ _row("read_ranges read_ranges_dev", i32, vp, u64, u32, u64p, u64p, u32p, u32, u6
 
 ABI_SYMBOLS = list(TABLE)      # every symbol include/nlzm_hip.h declares
 
+# include/nlzm_hip_elem.h, a header of its own (tests/test_elem_abi.py holds these rows to it as tests/test_abi.py holds the ones above to theirs)
+ELEM_TABLE: dict[str, tuple] = {}
+
+
+def _elem_row(names: str, restype, *argtypes) -> None:
+    for name in names.split():
+        ELEM_TABLE["nlzm_hip_" + name] = (restype, list(argtypes))
+
+
+_elem_row("plane_costs plane_costs_dev", i32, vp, u64, u32, u64p, u64p, u64p, u64p)
+_elem_row("choose_elem", u32, u64p, u64)
+_elem_row("choose_elems choose_elems_dev", i32, vp, u64, u32, u64p, u64p, u8p)
+_elem_row("compress_ranges_auto compress_ranges_auto_dev", i32, vp, u64, u32, u64p, u64p, u8p, u32, vp, u64, u64p, u64p)
+
+ELEM_SYMBOLS = list(ELEM_TABLE)
+
 
 def bind(lib: C.CDLL) -> C.CDLL:
-    """Give every table symbol that `lib` exports its restype and argtypes; a symbol it lacks is skipped (and fails where it is called)."""
-    for name, (restype, argtypes) in TABLE.items():
+    """Give every symbol of both tables that `lib` exports its restype and argtypes; a symbol it lacks is skipped (and fails where it is called)."""
+    for name, (restype, argtypes) in {**TABLE, **ELEM_TABLE}.items():
         try:
             f = getattr(lib, name)
         except AttributeError:

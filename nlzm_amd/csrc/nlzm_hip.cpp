@@ -22,6 +22,7 @@
 #include "nlzm_cut_host.h"
 #include "nlzm_dedup_host.h"
 #include "nlzm_planes_host.h"
+#include "nlzm_elem_host.h"
 #include "nlzm_report.h"
 #include "nlzm_stream_plan.h"
 
@@ -807,6 +808,7 @@ int nlzm_hip_get_counter(const char *key, uint64_t *value)
     if (!strncmp(key, "cut_", 4)) return nlzm::cut_counter(key, value);
     if (!strncmp(key, "dedup_", 6)) return nlzm::dedup_counter(key, value);
     if (!strncmp(key, "planes_", 7)) return nlzm::planes_counter(key, value);
+    if (!strncmp(key, "elem_", 5)) return nlzm::elem_counter(key, value);
     if (C.open) { const int rc = refresh_stats(C, D.opt.report != 0); if (rc) return rc; }
     if (compress_counter(key, C.prof_last, C.wc_last, C.stats.positions, value)) return 0;
     if (!strcmp(key, "block_pool_bytes")) { *value = D.blocks_pool_size; return 0; }
